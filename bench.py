@@ -10,11 +10,20 @@ rx buffer.  N GPUs: one process per GPU, disjoint batches (distinct seeds),
 no collectives on the data path (weak scaling); gloo carries only the
 barrier and the max-over-ranks time.
 
-Also reported (not `value`): a STREAM-style in-place ceiling on the same
-buffer, the host-memory-inclusive rate (pinned H2D -> scan -> unmask -> D2H,
-hvws_pipeline), and the reference CPU path (oracle/_ref: libhv's own
-websocket_parser.c driven through a restatement of WebSocketParser.cpp,
-8 KiB chunks) timed on this host on a bounded sample.
+A plain run does what `value` needs and no more: it builds the batch, warms
+up, times --steps steps, writes the last step's outputs when --dump-outputs
+is given, and prints the result line (the kernel times in it come from HIP
+events inside the timed steps).
+
+--full adds everything else, reported beside `value`: the digests of the
+batch against the reference's fixtures and the byte-exact check after the
+run, the other step call, a STREAM-style in-place ceiling on the same
+buffer, the event-loop, drop-in and transmit legs, the host-memory-inclusive
+rate (pinned H2D -> scan -> unmask -> D2H, hvws_pipeline), and the reference
+CPU path (oracle/_ref: libhv's own websocket_parser.c driven through a
+restatement of WebSocketParser.cpp, 8 KiB chunks) timed on this host on a
+bounded sample.  The options that size or switch those legs act under --full
+only.
 """
 from __future__ import annotations
 
@@ -49,6 +58,13 @@ def parse():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--segments", type=int, default=4096,
                     help="connections the batch is cut into (1 = one stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other check and measurement (reference digests, byte-exact check, "
+                         "STREAM ceiling, event-loop / drop-in / host-inclusive / transmit legs, CPU baseline); "
+                         "the options below that size them act under --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (frame table, "
+                         "per-segment frames, carry, a fixed sample of the rx bytes) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget for the CPU baseline (0: skip)")
     ap.add_argument("--cpu-sample-mib", type=int, default=256)
     ap.add_argument("--host-gib", type=float, default=4.0, help="host-inclusive sample size (0: skip)")
@@ -69,7 +85,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the rank launcher and the timing reductions: no GPU call, "
                          "no measurement (tests/test_distributed.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def visible_devices() -> int:
@@ -813,8 +832,66 @@ def per_rank_roofline(row) -> dict:
     ms, achieved, ceiling = (float(x) for x in row)
     return {"unmask_ms_mean": round(ms, 3),
             "roofline_frac": round(achieved / HBM_PEAK_GBS, 4),
-            "stream_ceiling_GBps": round(ceiling, 1),
+            "stream_ceiling_GBps": round(ceiling, 1) if ceiling > 0 else None,
             "frac_of_box_ceiling": round(achieved / ceiling, 4) if ceiling > 0 else None}
+
+
+DUMP_ROWS = 1 << 16     # table rows kept per dumped table
+DUMP_PIECE = 4096       # the rx sample: DUMP_PIECES pieces of DUMP_PIECE bytes
+DUMP_PIECES = 2048
+
+
+def dump_outputs(eng, rx, plan, nseg: int, out_dir: str, rank: int, world: int) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as
+    <out_dir>/<name>.npy (float64 tables, float32 bytes; every value is an
+    integer a float of that width holds exactly):
+      counts          [frames found, rx bytes, segments]
+      frames          (row, hdr_off, pay_off, pay_len, length, key, info) per frame
+      segment_frames  (segment, first frame, frame count) per segment
+      carry           (segment, state, flags, mask, mask_offset, length, require, started)
+      rx_offsets      where each piece of rx_sample starts in the rx buffer
+      rx_sample       the rx bytes (payloads unmasked in place) of those pieces
+    A table of more than DUMP_ROWS rows is cut to a sample of them, and an rx
+    buffer of more than DUMP_PIECES * DUMP_PIECE bytes to that many pieces:
+    first and last always, the rest drawn with a fixed seed, so two runs with
+    the same arguments dump the same rows and bytes (about 36 MB at most).
+    With N ranks each rank writes <name>_rank<r>.npy."""
+    import libhv_amd
+
+    L = libhv_amd.lib()
+    rng = np.random.default_rng(6455)
+
+    def pick(n: int, keep: int) -> np.ndarray:
+        if n <= keep:
+            return np.arange(n, dtype=np.int64)
+        return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, keep - 2)])).astype(np.int64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    fr = eng.frames()
+    out["counts"] = np.array([len(fr), plan.total, nseg], dtype=np.float64)
+    rows = pick(len(fr), DUMP_ROWS)
+    out["frames"] = np.column_stack([rows] + [fr[f][rows] for f in libhv_amd.FRAME_DTYPE.names]).astype(np.float64)
+    first, cnt = eng.segment_frames(nseg)
+    srows = pick(nseg, DUMP_ROWS)
+    out["segment_frames"] = np.column_stack([srows, first[srows], cnt[srows]]).astype(np.float64)
+    carry, started = eng.carry(nseg)
+    out["carry"] = np.array([(s,) + carry[s].fields() + (started[s],) for s in srows],
+                            dtype=np.float64).reshape(len(srows), 8)
+    if plan.total <= DUMP_PIECE * DUMP_PIECES:
+        offs, piece = np.zeros(1, dtype=np.int64), plan.total
+    else:
+        offs, piece = pick(plan.total - DUMP_PIECE + 1, DUMP_PIECES), DUMP_PIECE
+    sample = np.empty((len(offs), piece), dtype=np.uint8)
+    for i, o in enumerate(offs):
+        libhv_amd._check(L.hvws_d2h(eng.ctx, sample[i].ctypes.data, rx.ptr + int(o), piece), "hvws_d2h")
+        eng.sync()
+    out["rx_offsets"] = offs.astype(np.float64)
+    out["rx_sample"] = sample.astype(np.float32)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+    return {"dir": out_dir, "arrays": {name + sfx: list(a.shape) for name, a in out.items()}}
 
 
 def dry_run(args, rank: int, world: int, local: int, dist) -> None:
@@ -908,7 +985,8 @@ def main():
     P = plan.masked_payload_bytes()
     HB = plan.header_bytes
     segs = eng.prepare(plan.segments)   # ctypes tables built once, outside the timed loop
-    fx_name, fx = fixture_for(cfg, rank)
+    full = args.full
+    fx_name, fx = fixture_for(cfg, rank) if full else (None, None)
     if fx is not None:
         # the batch this rank built is the reference's (masked digest)
         d = f"{eng.digest(rx, plan.total):016x}"
@@ -959,11 +1037,14 @@ def main():
     unmask_ms = [t[1] for t in times if t[1] >= 0]   # the sampled steps
     if not unmask_ms:
         raise SystemExit(f"rank {rank}: no unmask timing events in the last {len(times)} steps")
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(eng, rx, plan, segs.n, args.dump_outputs, rank, world)
 
-    # The same number of steps through the other step call, for the record
-    # (pipelined vs serial); an even count keeps the parity of passes.
+    # Four steps through the other step call, for the record (pipelined vs
+    # serial); an even count keeps the parity of passes.
     other_ms = None
-    if rank == 0:
+    if rank == 0 and full:
         other = eng.step if not args.serial else eng.step_resident
         n_other = 4
         eng.sync()
@@ -976,8 +1057,8 @@ def main():
     # payload unmasked, an even number masked again (XOR is an involution).
     # Byte-exact against the plan (device synth VERIFY), and -- for c3-shaped
     # batches -- the whole buffer's digest against the reference's fixture.
-    passes = args.warmup + args.steps + (4 if rank == 0 else 0)
-    bad = eng.synth(rx, plan.total, plan.seed, dp, 2 if passes % 2 else 1)
+    passes = args.warmup + args.steps + (4 if other_ms is not None else 0)
+    bad = eng.synth(rx, plan.total, plan.seed, dp, 2 if passes % 2 else 1) if full else 0
     if bad:
         raise SystemExit(f"rank {rank}: {bad} bytes differ from the expected batch after {passes} passes")
     digest_ok = None
@@ -1006,20 +1087,25 @@ def main():
     # its own card on the same buffer (an even number of passes: no net
     # change), so an N-rank line shows each card's unmask time, its fraction
     # of 8 TB/s and of its own ceiling -- one slow card stands out.
-    eng.sync()
-    t = time.perf_counter()
-    reps = 4
-    for _ in range(reps):
-        eng.stream_xor(rx, plan.total & ~15, 0x5A5A5A5A)
-    eng.sync()
-    ceiling = 2 * (plan.total & ~15) * reps / (time.perf_counter() - t) / 1e9
+    ceiling = 0.0   # not measured (a plain run)
+    if full:
+        eng.sync()
+        t = time.perf_counter()
+        reps = 4
+        for _ in range(reps):
+            eng.stream_xor(rx, plan.total & ~15, 0x5A5A5A5A)
+        eng.sync()
+        ceiling = 2 * (plan.total & ~15) * reps / (time.perf_counter() - t) / 1e9
     prows = gather_rows(dist, [mean_unmask, achieved, ceiling])
 
     extra = {}
     sample = None
     feed_streams = feed_pay = None
     if rank == 0:
-        extra["stream_ceiling_GBps"] = round(ceiling, 1)
+        extra["full"] = full
+        extra["stream_ceiling_GBps"] = round(ceiling, 1) if full else None
+        if dumped is not None:
+            extra["dumped_outputs"] = dumped
         # pipelined steps record no scan-side timing markers (-1; include/hvws.h)
         scan_rec = [t for t in scan_ms if t >= 0]
         extra["scan_ms_mean"] = round(float(np.mean(scan_rec)), 3) if scan_rec else None
@@ -1050,8 +1136,8 @@ def main():
             "ranks": [{"rank": int(v[0]), "device": int(v[1]),
                        "fixture": (fixture_for(cfg, int(v[0]))[0] if v[2] >= 0 else None),
                        "digest_match": (bool(v[2]) if v[2] >= 0 else None)} for v in vrows],
-        }
-        if args.sweep_unmask:
+        } if full else None
+        if args.sweep_unmask and full:
             # every geometry, interleaved round by round in this process; an
             # even number of passes per geometry leaves the batch masked, which
             # is verified byte-for-byte afterwards
@@ -1088,10 +1174,10 @@ def main():
 
         # event loop, before the legs that allocate and
         # free large buffers: host-side rates measured after them ran slower
-        if args.feed_conns > 0:
+        if full and args.feed_conns > 0:
             extra["event_loop"], feed_streams, feed_pay = event_loop_leg(eng, device, args.feed_conns,
                                                                          args.feed_iters, plan.seed + 7)
-        if args.dropin_reads > 0:
+        if full and args.dropin_reads > 0:
             extra["drop_in"] = dropin_leg_child(device, plan.seed + 11, args.dropin_reads)
 
     rx_plain = passes % 2 == 1   # payloads currently unmasked
@@ -1101,13 +1187,13 @@ def main():
     # and went)
     if dist is not None:
         dist.barrier()   # rank 0's extra legs above
-    if args.host_gib > 0:
+    if full and args.host_gib > 0:
         res, sample = host_inclusive_leg(eng, plan, dp, rx, args, dist, rank, world, device)
         rx_plain = False
         if rank == 0:
             extra["host_inclusive"] = res
 
-    if rank == 0 and not args.no_tx:
+    if rank == 0 and full and not args.no_tx:
         extra["tx"] = tx_leg(eng, plan, dp, rx, rx_plain, segs, tpath)
 
     dp.free()

@@ -13,7 +13,7 @@ $S pytest_gpu_$TAG 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --ti
 [ -f gpurun_out/.stop ] && exit 1
 $S smoke_$TAG 300 python3 scripts/smoke_run.py
 [ -f gpurun_out/.stop ] && exit 1
-$S bench_$TAG 400 python3 bench.py
+$S bench_$TAG 400 python3 bench.py --full
 [ -f gpurun_out/.stop ] && exit 1
 for run in 1 0; do
   $S c2_run${run}_$TAG 180 env HVWS_RUN=$run python3 bench.py --config c2 --steps 200 --warmup 10 --no-tx --feed-conns 0 --dropin-reads 0 --host-gib 0 --cpu-seconds 0
@@ -27,5 +27,5 @@ done
 # the drop-in's resident worker included (its HSA queue is destroyed at exit)
 $S c4_one_$TAG 240 python3 bench.py --config c4 --segments 1 --steps 40 --warmup 5 --no-tx --feed-conns 0 --dropin-reads 0 --host-gib 0 --cpu-seconds 0
 [ -f gpurun_out/.stop ] && exit 1
-$S kt_$TAG 400 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_kt -o kt -- python3 bench.py
+$S kt_$TAG 400 rocprofv3 --kernel-trace --stats -d rocprof_out/${TAG}_kt -o kt -- python3 bench.py --full
 exit 0

@@ -9,5 +9,5 @@ $S pytest_gpu_$TAG 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --ti
 [ -f gpurun_out/.stop ] && exit 1
 $S smoke_$TAG 300 python3 scripts/smoke_run.py
 [ -f gpurun_out/.stop ] && exit 1
-$S bench_$TAG 400 python3 bench.py
+$S bench_$TAG 400 python3 bench.py --full
 exit 0

@@ -152,6 +152,16 @@ def test_bench_launcher_refuses_ranks_sharing_a_device():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_full_and_dump_options_reach_the_ranks(tmp_path):
+    """--full and --dump-outputs DIR are options of every run, passed on to
+    the ranks the launcher starts; --steps 0 is refused before anything runs."""
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len([ln for ln in p.stdout.splitlines() if ln.startswith("{")]) == 1
+    p = _bench(["--gpus", "1", "--steps", "0", "--dry-run"], timeout=60)
+    assert p.returncode == 2 and "--steps" in p.stderr and not p.stdout.strip()
+
+
 def test_bus_id_round_trip():
     sys.path.insert(0, ROOT)
     import bench
