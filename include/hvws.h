@@ -325,7 +325,9 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
                       uint64_t* out_len);
 /* Device time (ms, HIP events on the ctx stream) of the last hvws_encode_keys
  * kernel, or of the last hvws_build_frames' device work after its size check
- * (tile index, source spans, k_build); the default build geometry's name. */
+ * (tile index, source spans, k_build), or of the last hvws_utf8 (its tile
+ * index and all three kernels) -- whichever was called last; the default
+ * build geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
 const char* hvws_build_kernel_name(void);
 /* The k_build geometry the last hvws_build_frames on ctx ran: one-wave
@@ -367,6 +369,87 @@ int hvws_rx_batch(hvws_ctx* ctx, uint8_t* h_rx, uint64_t len, const hvws_segment
  * validation state in the padding byte after websocket_parser.mask_offset.
  * Returns the previous classes. */
 uint32_t hvws_set_validation(hvws_ctx* ctx, uint32_t classes);
+
+/* ---- UTF-8 validation of text messages, device resident ---------------- */
+/* RFC 6455 sec. 5.6 / 8.1: a text message must be valid UTF-8 (RFC 3629).  The
+ * reference does not check this; like hvws_set_validation it is new behaviour
+ * a caller opts into, here by calling hvws_utf8 after a scan or step.
+ *
+ * The validator is a state machine over the payload bytes.  Its states say
+ * what the next byte must be:
+ *    0 HVWS_U8_ACCEPT  character boundary
+ *    1                 one continuation 80..BF, then 0
+ *    2                 80..BF, then 1
+ *    3                 after E0: A0..BF, then 1
+ *    4                 after ED: 80..9F, then 1
+ *    5                 after F0: 90..BF, then 2
+ *    6                 after F1..F3: 80..BF, then 2
+ *    7                 after F4: 80..8F, then 2
+ *   15 HVWS_U8_REJECT  sticky
+ * and from state 0: 00..7F -> 0, C2..DF -> 1, E0 -> 3, E1..EC / EE / EF -> 2,
+ * ED -> 4, F0 -> 5, F1..F3 -> 6, F4 -> 7, anything else -> 15.
+ *
+ * The transition word of a byte string holds, in nibble k (bits 4k..4k+3), the
+ * state the string leaves the machine in when it is entered in state k
+ * (k = 0..7).  The empty string gives HVWS_U8_IDENTITY; "abc" gives
+ * 0xfffffff0; the bytes 82 AC give 0x11f0f0ff.  Words compose: a then b is
+ * nibble-wise b[a[k]], and REJECT stays REJECT.  hvws_utf8 computes one word
+ * per frame record of the last scan (the record's payload bytes inside the
+ * batch; a record without payload bytes has the identity word), whatever the
+ * frame's opcode, and then folds each segment's words in record order.
+ *
+ * The fold keeps one state word per segment (= per connection): bits 0-3 the
+ * state above, bit 4 HVWS_U8_TEXT_OPEN (a text message is in progress); 0 is a
+ * fresh connection.  For each record of the segment, in order, with
+ * op = info & 0xF and fin = info & 0x10:
+ *   - op >= 8 or op in 3..7: the record is skipped (control frames between the
+ *     fragments of a message);
+ *   - op == 1 with HVWS_I_HDR: text opens, state = ACCEPT (an unfinished
+ *     earlier message is a protocol error of another kind: restart);
+ *   - op == 2 with HVWS_I_HDR: text closes, state = ACCEPT;
+ *   - op == 0, or a record without HVWS_I_HDR, keeps what is open (a lone
+ *     continuation with nothing open is ignored);
+ *   - text open and HVWS_I_BODY: state = word[state];
+ *   - HVWS_I_END and fin with text open: a state other than ACCEPT becomes
+ *     REJECT (a character truncated by the end of the message); text closes.
+ * bad[s] is the index (in the batch's frame table) of the first record at
+ * which the state became REJECT, or HVWS_U8_NONE.  REJECT is sticky: later
+ * records change neither the state word nor bad[s], and the state word is then
+ * HVWS_U8_REJECT alone (bit 4 clear), so the result does not depend on where
+ * the batches cut the stream.  A state word carried in with REJECT (or with
+ * 8..14, which are no states) gives bad[s] = the segment's first record index
+ * (even when the segment has no records) and carries out REJECT.  A Close
+ * frame's reason text is not checked.
+ *
+ * An event loop keeps one uint32_t per connection next to its
+ * websocket_parser carry: 0 at accept, state_in[s] on the way in, state_out[s]
+ * on the way out, and fails the connection (close code 1007) when bad[s] is
+ * not HVWS_U8_NONE. */
+#define HVWS_U8_ACCEPT    0u
+#define HVWS_U8_REJECT    15u
+#define HVWS_U8_TEXT_OPEN (1u << 4)
+#define HVWS_U8_IDENTITY  0x76543210u
+#define HVWS_U8_NONE      UINT64_MAX
+/* After hvws_scan / hvws_step[_resident] of d_rx (same buffer and length as the last
+ * scan, else HVWS_EINVAL; none before it: HVWS_EINVAL). masked: 1 = masked payloads
+ * are still masked (after hvws_scan), 0 = already unmasked (after a step).
+ * state_in: host, nseg words, NULL = all 0. Asynchronous on the ctx stream.
+ * The buffer is only read.  After a RUN step the frame records are built first
+ * (as for hvws_get_frames). */
+int hvws_utf8(hvws_ctx* ctx, const uint8_t* d_rx, uint64_t rx_len, int masked, const uint32_t* state_in);
+/* Results of the last hvws_utf8 on ctx, valid until the next one.  Both wait
+ * for it.  hvws_get_utf8_words: the words of records first .. first + n - 1
+ * (HVWS_EINVAL beyond that batch's record count).  hvws_get_utf8: per segment
+ * of that batch, the state word to carry into the connection's next batch and
+ * bad[s] (either may be NULL). */
+int hvws_get_utf8_words(hvws_ctx* ctx, uint32_t* out, uint64_t first, uint64_t n);
+int hvws_get_utf8(hvws_ctx* ctx, uint32_t* state_out, uint64_t* bad);
+/* Records of the batch the last hvws_utf8 ran over (-1: none yet); waits.  The
+ * words outlive the next scans, hvws_frame_count does not. */
+int64_t hvws_utf8_count(hvws_ctx* ctx);
+/* Bytes of the batch one workgroup of the word kernel covers (tests place
+ * payload bytes around its multiples). */
+uint64_t hvws_utf8_tile(void);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

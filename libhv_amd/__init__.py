@@ -149,6 +149,11 @@ _SIGS = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
     ),
     "hvws_last_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "hvws_utf8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
+    "hvws_get_utf8_words": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "hvws_get_utf8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_utf8_tile": (ctypes.c_uint64, []),
+    "hvws_utf8_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -464,6 +469,34 @@ class Engine:
         out = ctypes.c_float(0)
         _check(lib().hvws_last_kernel_ms(self.ctx, ctypes.byref(out)), "hvws_last_kernel_ms")
         return float(out.value)
+
+    def utf8(self, rx: DeviceBuffer, rx_len: int, masked: bool, state_in=None) -> None:
+        """hvws_utf8 over the last scan / step of rx: per-record transition words,
+        then each segment's fold from state_in (one word per segment; None = 0)."""
+        st = None
+        if state_in is not None:
+            st = np.ascontiguousarray(state_in, dtype=np.uint32)
+        _check(lib().hvws_utf8(self.ctx, rx.ptr, rx_len, int(bool(masked)), st.ctypes.data if st is not None else None),
+               "hvws_utf8")
+
+    def utf8_words(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Transition words of the last utf8() call's records (all of them by default)."""
+        if n is None:
+            total = lib().hvws_utf8_count(self.ctx)
+            if total < 0:
+                _check(-2, "hvws_utf8_count")
+            n = total - first
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        _check(lib().hvws_get_utf8_words(self.ctx, out.ctypes.data, first, max(n, 0)), "hvws_get_utf8_words")
+        return out
+
+    def utf8_result(self, nseg: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(state_out, bad) of the last utf8() call: per segment, the state word to
+        carry into its next batch and the first rejecting record (U8_NONE if none)."""
+        st = np.zeros(max(nseg, 1), dtype=np.uint32)
+        bad = np.zeros(max(nseg, 1), dtype=np.uint64)
+        _check(lib().hvws_get_utf8(self.ctx, st.ctypes.data, bad.ctypes.data), "hvws_get_utf8")
+        return st[:nseg], bad[:nseg]
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

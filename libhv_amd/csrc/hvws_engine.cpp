@@ -232,6 +232,15 @@ struct hvws_ctx {
     dbuf stage;
     dbuf xor_stage;
     dbuf synth_sizes, synth_tiles, synth_bad;
+    // hvws_utf8: per-record words and interior flags (zero between passes),
+    // its tile index, {record count}, per-segment state in / out and verdicts;
+    // state_in goes up through a pinned slot, reusable once its copy has run
+    dbuf u8_words, u8_flags, u8_tiles, u8_meta, u8_in, u8_out, u8_bad;
+    hbuf h_u8_in;
+    hipEvent_t u8_up_ev = nullptr;
+    bool u8_up_pending = false;
+    bool have_u8 = false;
+    uint32_t u8_nseg = 0;
     // small-batch path (k_small): upload packet, record slots, pinned results
     hbuf h_small_in, h_small_out;
     hbuf h_small_done;             // per-segment completion words k_small writes last
@@ -2252,7 +2261,8 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         for (dbuf* b : {&c->pipe_slot[0], &c->pipe_slot[1], &c->pipe_slot[2], &c->pipe_segs}) b->release();
         for (dbuf* b : {&c->segs, &c->carry_in, &c->stage, &c->xor_stage, &c->synth_sizes, &c->synth_tiles, &c->synth_bad,
                         &c->tx_size, &c->tx_off, &c->tx_scan, &c->tx_tiles, &c->tx_stat, &c->tx_span, &c->d_small_in,
-                        &c->d_small_slots})
+                        &c->d_small_slots, &c->u8_words, &c->u8_flags, &c->u8_tiles, &c->u8_meta, &c->u8_in, &c->u8_out,
+                        &c->u8_bad})
             b->release();
         c->chk.release();
     }
@@ -2264,6 +2274,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->h_small_done.release();
         c->h_small_out.release();
         c->h_feed.release();
+        c->h_u8_in.release();
         c->h_segs.release();
         for (hbuf& b : c->h_up) b.release();
         c->h_total.release();
@@ -2275,6 +2286,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         for (tset& t : c->ts)
             if (t.free_ev) hipEventDestroy(t.free_ev);
         if (c->sv_ev) hipEventDestroy(c->sv_ev);
+        if (c->u8_up_ev) hipEventDestroy(c->u8_up_ev);
         for (hipEvent_t ev : c->pipe_ev)
             if (ev) hipEventDestroy(ev);
         for (auto& ev : c->ev)
@@ -2520,6 +2532,113 @@ int hvws_scan(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, const hvws_segm
 }
 
 int hvws_unmask(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len) { return unmask_impl(c, d_rx, rx_len); }
+
+// UTF-8 validation over the last scan's frame table (hvws_utf8.hip): tile
+// index at U8_TILE, words, fold -- all on the context stream, behind the scan
+// (and the unmask of a step), reading rx and the current table set only.
+int hvws_utf8(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, const uint32_t* state_in) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_utf8 without a preceding hvws_scan");
+    if (!d_rx || d_rx != c->rx || rx_len != c->rx_len)
+        return set_err(HVWS_EINVAL, "hvws_utf8 buffer differs from the scanned one");
+    // a RUN step left no frame table: build it now (as hvws_unmask does)
+    if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
+    const uint32_t nseg = c->nseg;
+    // c->nfr: the record count, or its bound while the count is on the device
+    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
+    const uint64_t ntiles = (rx_len + U8_TILE - 1) / U8_TILE;
+    HIP_OR(c->u8_words.ensure(cap * 4 + 16), HVWS_ENOMEM);
+    {
+        const void* was = c->u8_flags.p;
+        const uint64_t had = c->u8_flags.cap;
+        HIP_OR(c->u8_flags.ensure(cap * 4 + 16), HVWS_ENOMEM);
+        if (c->u8_flags.p != was || c->u8_flags.cap != had)
+            HIP_OR(hipMemsetAsync(c->u8_flags.p, 0, c->u8_flags.cap, c->stream), HVWS_EHIP);
+    }
+    HIP_OR(c->u8_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
+    HIP_OR(c->u8_meta.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->u8_in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->u8_out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->u8_bad.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    if (state_in && nseg) {
+        if (!c->u8_up_ev) HIP_OR(hipEventCreateWithFlags(&c->u8_up_ev, hipEventDisableTiming), HVWS_EHIP);
+        if (c->u8_up_pending) {   // the previous pass's copy out of the slot
+            HIP_OR(hipEventSynchronize(c->u8_up_ev), HVWS_EHIP);
+            c->u8_up_pending = false;
+        }
+        HIP_OR(c->h_u8_in.ensure((uint64_t)nseg * 4), HVWS_ENOMEM);
+        memcpy(c->h_u8_in.p, state_in, (uint64_t)nseg * 4);
+        HIP_OR(hipMemcpyAsync(c->u8_in.p, c->h_u8_in.p, (uint64_t)nseg * 4, hipMemcpyHostToDevice, c->stream),
+               HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->u8_up_ev, c->stream), HVWS_EHIP);
+        c->u8_up_pending = true;
+    }
+    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    if (ntiles)
+        HIP_OR(launch_tile_index(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), 0, c->T().total.as<uint64_t>(),
+                                 c->u8_tiles.as<uint32_t>(), ntiles, U8_TILE, c->stream),
+               HVWS_EHIP);
+    HIP_OR(launch_utf8(d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
+                       c->T().f_keyrot.as<uint32_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(), cap,
+                       c->u8_tiles.as<uint32_t>(), ntiles, masked, c->u8_flags.as<uint32_t>(),
+                       c->u8_words.as<uint32_t>(), c->u8_meta.as<uint64_t>(), c->T().counts.as<uint64_t>(),
+                       c->T().bases.as<uint64_t>(), nseg, state_in ? c->u8_in.as<uint32_t>() : nullptr,
+                       c->u8_out.as<uint32_t>(), c->u8_bad.as<uint64_t>(), c->stream),
+           HVWS_EHIP);
+    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
+    c->ev_build = true;
+    // Pipelined steps: the scan two steps on writes this table set and must
+    // wait for this pass as it waits for the set's unmask.
+    if (c->piped) {
+        HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
+        c->T().free_wait = c->T().free_ev;
+        c->T().free_pending = true;
+    }
+    c->have_u8 = true;
+    c->u8_nseg = nseg;
+    return HVWS_OK;
+}
+
+int64_t hvws_utf8_count(hvws_ctx* c) {
+    if (!c || !c->have_u8 || check_ctx(c) != HVWS_OK) return -1;
+    uint64_t nrec = 0;
+    if (hipMemcpyAsync(&nrec, c->u8_meta.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_err(HVWS_EHIP, "hvws_utf8_count: reading the count failed");
+        return -1;
+    }
+    return (int64_t)nrec;
+}
+
+int hvws_get_utf8_words(hvws_ctx* c, uint32_t* out, uint64_t first, uint64_t n) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_u8) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
+    const int64_t have = hvws_utf8_count(c);
+    if (have < 0) return HVWS_EHIP;
+    const uint64_t nrec = (uint64_t)have;
+    if (first > nrec || n > nrec - first) return set_err(HVWS_EINVAL, "word range out of bounds");
+    if (n == 0) return HVWS_OK;
+    if (!out) return set_err(HVWS_EINVAL, "null output");
+    HIP_OR(hipMemcpyAsync(out, c->u8_words.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int hvws_get_utf8(hvws_ctx* c, uint32_t* state_out, uint64_t* bad) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_u8) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
+    const uint64_t nseg = c->u8_nseg;
+    if (state_out && nseg)
+        HIP_OR(hipMemcpyAsync(state_out, c->u8_out.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (bad && nseg) HIP_OR(hipMemcpyAsync(bad, c->u8_bad.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+uint64_t hvws_utf8_tile(void) { return U8_TILE; }
 
 int hvws_step_resident(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, const hvws_segment* segs,
                        const websocket_parser* carry_in, uint32_t nseg) {
@@ -2985,7 +3104,7 @@ int hvws_encode_keys(hvws_ctx* c, const char* d_keys, const uint64_t* d_key_off,
 int hvws_last_kernel_ms(hvws_ctx* c, float* ms) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!c->ev_build) return set_err(HVWS_EINVAL, "no build_frames / encode_keys call yet");
+    if (!c->ev_build) return set_err(HVWS_EINVAL, "no build_frames / encode_keys / utf8 call yet");
     HIP_OR(hipEventSynchronize(c->ev[5]), HVWS_EHIP);
     HIP_OR(hipEventElapsedTime(ms, c->ev[4], c->ev[5]), HVWS_EHIP);
     return HVWS_OK;

@@ -467,6 +467,22 @@ void par_memcpy(void* dst, const void* src, uint64_t n);
 // Batched handshake digest (hvws_keys.hip): accept[32*i..] = base64(SHA-1(key_i + GUID)), 28 chars + 4 zero bytes.
 hipError_t launch_encode_keys(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len, uint64_t n,
                               uint8_t* accept, hipStream_t st);
+// UTF-8 validation of text messages (hvws_utf8.hip; include/hvws.h has the
+// state machine, the transition words and the fold rules).  Reads rx and the
+// frame table only.  nfr_dev: the batch's record count on the device, clamped
+// to cap (the entries words / flags hold).  tile_first: ntiles + 1 entries of
+// launch_tile_index at U8_TILE.  flags: one word per record, all zero on
+// entry (the caller zeroes a new array), set by k_u8_tiles where a payload's
+// interior (bytes 3 ..) breaks a character and cleared again by k_u8_words.
+// meta[0] receives the clamped record count.  Then the per-segment fold:
+// state_in (nullptr: all 0) -> state_out, bad.
+constexpr uint64_t U8_TILE = 16384;   // 256 threads x 4 chunks of 16 B
+constexpr uint32_t U8_ACCEPT = 0u, U8_REJECT = 15u, U8_TEXT_OPEN = 16u, U8_IDENTITY = 0x76543210u;
+hipError_t launch_utf8(const uint8_t* rx, uint64_t rx_len, const uint64_t* pay_off, const uint64_t* pay_len,
+                       const uint32_t* keyrot, const uint32_t* info, const uint64_t* nfr_dev, uint64_t cap,
+                       const uint32_t* tile_first, uint64_t ntiles, int masked, uint32_t* flags, uint32_t* words,
+                       uint64_t* meta, const uint64_t* counts, const uint64_t* bases, uint32_t nseg,
+                       const uint32_t* state_in, uint32_t* state_out, uint64_t* bad, hipStream_t st);
 // Predicted frames above which a uniform segment is verified grid-wide (k_verify).
 uint64_t spec_min();
 uint64_t set_spec_min(uint64_t v);   // 0 = default; returns the previous value
