@@ -70,6 +70,13 @@ struct dbuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
+    // ensure(), with a new allocation zeroed on st (arrays the kernels leave zero between uses)
+    hipError_t ensure_zeroed(uint64_t bytes, hipStream_t st) {
+        const void* was = p;
+        const uint64_t had = cap;
+        const hipError_t e = ensure(bytes);
+        return e == hipSuccess && (p != was || cap != had) ? hipMemsetAsync(p, 0, cap, st) : e;
+    }
     void release() {
         if (p) {
             door_park_device();
@@ -206,7 +213,7 @@ struct hvws_ctx {
     int run_mode = -1;         // hvws_set_run: -1 auto, 0 never, 1 whenever a step's batch allows it
     uint32_t run_skip = 0;     // steps left before RUN is tried again after a failed hypothesis
     uint64_t run_seq = 0;      // the current RUN step's verdict number
-    uint64_t run_seen = 0;     // the last verdict read (status pad3)
+    uint64_t run_seen = 0;     // the last verdict read (dspec_status::run_seq)
     uint64_t last_mean = 0;    // bytes per record of the last exact (or SPEC) scan: RUN is for small frames
     // frame sieve (hvws_sieve.hip): one long mixed-size segment discovered in
     // parallel.  h_sv receives the device state + survivor and chain counts
@@ -345,30 +352,21 @@ bool table_checks() {
 namespace {
 
 dframes frames_of(hvws_ctx* c) {
-    dframes f;
-    f.hdr_off = c->T().f_hdr.as<int64_t>();
-    f.pay_off = c->T().f_off.as<uint64_t>();
-    f.pay_len = c->T().f_len.as<uint64_t>();
-    f.length = c->T().f_length.as<uint64_t>();
-    f.key = c->T().f_key.as<uint32_t>();
-    f.keyrot = c->T().f_keyrot.as<uint32_t>();
-    f.info = c->T().f_info.as<uint32_t>();
-    f.cap = c->T().frame_cap;
-    return f;
+    tset& t = c->T();
+    return {t.f_hdr.as<int64_t>(), t.f_off.as<uint64_t>(), t.f_len.as<uint64_t>(), t.f_length.as<uint64_t>(),
+            t.f_key.as<uint32_t>(), t.f_keyrot.as<uint32_t>(), t.f_info.as<uint32_t>(), t.frame_cap};
 }
 
 hipError_t ensure_frames(hvws_ctx* c, uint64_t n, bool exact = false) {
     if (n <= c->T().frame_cap && c->T().f_off.p) return hipSuccess;
     uint64_t want = std::max<uint64_t>(exact ? n : n + n / 4, 1024);
     hipError_t e;
-    if ((e = c->T().f_hdr.ensure(want * 8)) != hipSuccess) return e;
-    if ((e = c->T().f_off.ensure(want * 8)) != hipSuccess) return e;
-    if ((e = c->T().f_len.ensure(want * 8)) != hipSuccess) return e;
-    if ((e = c->T().f_length.ensure(want * 8)) != hipSuccess) return e;
-    if ((e = c->T().f_key.ensure(want * 4)) != hipSuccess) return e;
-    if ((e = c->T().f_keyrot.ensure(want * 4)) != hipSuccess) return e;
-    if ((e = c->T().f_info.ensure(want * 4)) != hipSuccess) return e;
-    c->T().frame_cap = want;
+    tset& t = c->T();
+    for (dbuf* b : {&t.f_hdr, &t.f_off, &t.f_len, &t.f_length})
+        if ((e = b->ensure(want * 8)) != hipSuccess) return e;
+    for (dbuf* b : {&t.f_key, &t.f_keyrot, &t.f_info})
+        if ((e = b->ensure(want * 4)) != hipSuccess) return e;
+    t.frame_cap = want;
     return hipSuccess;
 }
 
@@ -400,6 +398,14 @@ void from_dcarry(const dcarry& d, websocket_parser& p) {
 int check_ctx(hvws_ctx* c) {
     if (!c) return set_err(HVWS_EINVAL, "null context");
     HIP_OR(hipSetDevice(c->device), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+// ... and the batch arguments of hvws_scan / hvws_step / hvws_step_resident.
+int check_batch_args(hvws_ctx* c, const uint8_t* d_rx, const hvws_segment* segs, uint32_t nseg) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!segs && nseg) return set_err(HVWS_EINVAL, "null segment table");
+    if (((uintptr_t)d_rx & 15u) != 0) return set_err(HVWS_EINVAL, "rx buffer must be 16-byte aligned");
     return HVWS_OK;
 }
 
@@ -462,26 +468,20 @@ int step_times_at(hvws_ctx* c, int slot, float* out) {
     return HVWS_OK;
 }
 
-// Wait until k_spec_check has published scan `seq` in the (fine-grained)
-// pinned status: the device stores it with system-scope release as its last
-// write, so the host polls it instead of a stream event (an event marker
-// costs ~10 us of device idle between the check and the tile kernels).  A
-// stream that drains without publishing is an error, never a hang.
-// Pipelined SPEC steps queue the unmask after the host has seen the scan
-// finish instead of behind a cross-stream event ($HVWS_EXPERIMENT host_order=0: the
-// event, as in round 3).
 // $HVWS_RUN=0: the RUN path off (A/B runs); hvws_set_run overrides per context.
 bool run_env() {
     static const int v = getenv("HVWS_RUN") ? atoi(getenv("HVWS_RUN")) : 1;
     return v != 0;
 }
 
-
-// Pipelined steps: the host queues the unmask once the scan's last kernel
-// has published (always since round 4; round 6 removed the switch back to a
-// cross-stream event).
-constexpr bool host_order() { return true; }
-
+// Wait until k_spec_check has published scan `seq` in the (fine-grained)
+// pinned status: the device stores it with system-scope release as its last
+// write, so the host polls it instead of a stream event (an event marker
+// costs ~10 us of device idle between the check and the tile kernels).  A
+// stream that drains without publishing is an error, never a hang.
+// tiles: wait for tseq instead, published after the scan's last kernel
+// (launch_publish_tiles) -- pipelined SPEC and RUN steps queue the unmask
+// once the host has seen it, not behind a cross-stream event.
 int wait_status(hvws_ctx* c, uint64_t seq, bool tiles = false) {
     const dspec_status* st = c->h_status.as<dspec_status>();
     const uint64_t* w = tiles ? &st->tseq : &st->seq;
@@ -547,7 +547,7 @@ int ensure_sieve(hvws_ctx* c, uint64_t rx_len, sieve_bufs& b) {
     // never counted survivors -- means the full capacity)
     uint64_t capc = seen_s ? std::min<uint64_t>(cap, std::max<uint64_t>(1ull << 16, seen_s + seen_s / 4 + 1024))
                            : cap;
-    b.scr = nullptr;
+    uint64_t scr_bytes = 0;
     b.lgP = 0;
     if (b.rt != b.wt && seen_s) {
         // Windowed: survivors lie in the windows only (a count from a scan of
@@ -559,30 +559,33 @@ int ensure_sieve(hvws_ctx* c, uint64_t rx_len, sieve_bufs& b) {
         uint32_t lgP = 4;
         while (lgP < 12 && (1ull << lgP) < 2 * sieve_hops()) ++lgP;
         if ((capc << lgP) <= (1ull << 25)) {
-            HIP_OR(c->sv_scr.ensure((capc << lgP) * 8), HVWS_ENOMEM);
-            b.scr = c->sv_scr.as<uint64_t>();
+            scr_bytes = (capc << lgP) * 8;
             b.lgP = lgP;
         }
     }
     c->sv_capc = capc;
     const uint64_t ntm = sieve_tiles_max(rx_len);
     const uint64_t nmax = std::max(cap, ntm);
-    HIP_OR(c->sv_state.ensure(sizeof(dsieve)), HVWS_ENOMEM);
-    HIP_OR(c->sv_tcount.ensure(ntm * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_tbase.ensure(ntm * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_slot.ensure(sieve_slot_words(rx_len) * 4), HVWS_ENOMEM);
-    HIP_OR(c->sv_S.ensure(capc * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_Spre.ensure(cap * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_pool.ensure(cap * 4), HVWS_ENOMEM);
-    HIP_OR(c->sv_keep.ensure(cap * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_kbase.ensure(cap * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_J0.ensure(capc * 4), HVWS_ENOMEM);
-    HIP_OR(c->sv_J1.ensure(capc * 4), HVWS_ENOMEM);
-    HIP_OR(c->sv_mark.ensure(capc * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_hops.ensure(capc * 4), HVWS_ENOMEM);
-    HIP_OR(c->sv_rank.ensure(capc * 8), HVWS_ENOMEM);
-    HIP_OR(c->sv_cnt.ensure(32), HVWS_ENOMEM);
-    HIP_OR(c->sv_tmp.ensure((4 * ((nmax + 1023) / 1024) + 64) * 8), HVWS_ENOMEM);
+    // Every sieve buffer with the bytes this scan needs of it (0: not used).
+    // No room for one of them: the tables are released, the state and the
+    // counters stay, and the caller walks instead.
+    const struct { dbuf* b; uint64_t bytes; } need[] = {{&c->sv_scr, scr_bytes},        {&c->sv_state, sizeof(dsieve)},
+                {&c->sv_tcount, ntm * 8},       {&c->sv_tbase, ntm * 8},
+                {&c->sv_slot, sieve_slot_words(rx_len) * 4},
+                {&c->sv_S, capc * 8},           {&c->sv_Spre, cap * 8},
+                {&c->sv_pool, cap * 4},         {&c->sv_keep, cap * 8},
+                {&c->sv_kbase, cap * 8},        {&c->sv_J0, capc * 4},
+                {&c->sv_J1, capc * 4},          {&c->sv_mark, capc * 8},
+                {&c->sv_hops, capc * 4},        {&c->sv_rank, capc * 8},
+                {&c->sv_cnt, 32},               {&c->sv_tmp, (4 * ((nmax + 1023) / 1024) + 64) * 8}};
+    for (const auto& n : need) {
+        if (!n.bytes || n.b->ensure(n.bytes) == hipSuccess) continue;
+        (void)hipGetLastError();
+        for (const auto& r : need)
+            if (r.b != &c->sv_state && r.b != &c->sv_cnt) r.b->release();
+        return set_err(HVWS_ENOMEM, "no room for the sieve's tables");
+    }
+    b.scr = scr_bytes ? c->sv_scr.as<uint64_t>() : nullptr;
     b.state = c->sv_state.as<dsieve>();
     b.tcount = c->sv_tcount.as<uint64_t>();
     b.tbase = c->sv_tbase.as<uint64_t>();
@@ -612,8 +615,8 @@ int ensure_sieve(hvws_ctx* c, uint64_t rx_len, sieve_bufs& b) {
 
 // Unmask kernel launch with its timing events (no argument checks).  The
 // events ride on the unmask's own dispatch (launch_unmask).
-// joined = false: the host has already seen the scan's last kernel publish
-// (host_order), so the unmask needs no cross-stream wait packet.
+// joined = true: the host has already seen the scan's last kernel publish
+// (wait_status on tseq), so no cross-stream wait is queued before the unmask.
 hipError_t issue_unmask(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, bool joined = false) {
     hipError_t e;
     const bool piped = c->cs != c->stream;
@@ -643,44 +646,416 @@ hipError_t issue_unmask(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, bool joined
     // An untimed pipelined step attaches its set's free event to its last
     // dispatch (RUN: the repair) instead of recording it in a marker packet after it:
     // c2 0.355-0.356 vs 0.358 ms per step (profiles/r5_raw/events, fa*).
-    const bool attach_free = piped && !timed;
-    if (c->run_active) {   // the RUN unmask and its repair pass (the stop event rides on the repair)
-        if ((e = launch_unmask_run(d_rx, rx_len, c->T().runs.as<drun>(), c->T().run_trun.as<dtrun>(),
-                                   c->nseg, c->T().run_fail.as<uint32_t>(), mapped<dspec_status>(c->h_status),
-                                   c->run_seq, c->stream, timed ? c->tev[c->t_cur][2] : nullptr,
-                                   timed ? c->tev[c->t_cur][3] : (attach_free ? c->T().free_ev : nullptr))) !=
-            hipSuccess)
-            return e;
-    } else if ((e = launch_unmask(c->variant, d_rx, rx_len, frames_of(c), c->T().tile_first.as<uint32_t>(),
-                                  c->T().tile_key.as<uint32_t>(), c->T().tile_kind.as<uint8_t>(),
-                                  c->T().total.as<uint64_t>(), c->stream, pieces, timed ? c->tev[c->t_cur][2] : nullptr,
-                                  timed ? c->tev[c->t_cur][3] : (attach_free ? c->T().free_ev : nullptr))) !=
-               hipSuccess) {
-        return e;
-    }
+    const hipEvent_t ev_start = timed ? c->tev[c->t_cur][2] : nullptr;
+    const hipEvent_t ev_stop = timed ? c->tev[c->t_cur][3] : (piped ? c->T().free_ev : nullptr);
+    if (c->run_active)   // the RUN unmask and its repair pass (the stop event rides on the repair)
+        e = launch_unmask_run(d_rx, rx_len, c->T().runs.as<drun>(), c->T().run_trun.as<dtrun>(), c->nseg,
+                              c->T().run_fail.as<uint32_t>(), mapped<dspec_status>(c->h_status), c->run_seq, c->stream,
+                              ev_start, ev_stop);
+    else
+        e = launch_unmask(c->variant, d_rx, rx_len, frames_of(c), c->T().tile_first.as<uint32_t>(),
+                          c->T().tile_key.as<uint32_t>(), c->T().tile_kind.as<uint8_t>(), c->T().total.as<uint64_t>(),
+                          c->stream, pieces, ev_start, ev_stop);
+    if (e != hipSuccess) return e;
     if (timed) c->t_rec[c->t_cur] |= (uint8_t)(4u | 8u);
     c->t_unmask[c->t_cur] = true;
     if (piped) {   // the next pipelined scan into this set waits for this unmask
         // The unmask's dispatch-attached stop event marks the set free when it
         // was recorded; a separate marker packet cost ~6 us of device time per
         // pipelined c2 step (0.4215 -> 0.416 ms, profiles/r2r_raw).
-        if (timed) {
-            c->T().free_wait = c->tev[c->t_cur][3];
-        } else if (attach_free) {   // recorded by the repair's dispatch
-            c->T().free_wait = c->T().free_ev;
-        } else {
-            if ((e = hipEventRecord(c->T().free_ev, c->stream)) != hipSuccess) return e;
-            c->T().free_wait = c->T().free_ev;
-        }
+        c->T().free_wait = timed ? c->tev[c->t_cur][3] : c->T().free_ev;
         c->T().free_pending = true;
     }
     return hipSuccess;
 }
 
-// unmask_into: the caller will unmask d_rx right after the scan (hvws_step).
-// On the speculative path the unmask is then queued before the host waits
-// for the device's check -- a rejected table has a zero count, so that
-// unmask does nothing -- and *unmasked reports whether it stands.
+// One scan's inputs and working state, handed to the per-path functions below.
+struct scan_job {
+    hvws_ctx* c;
+    const uint8_t* d_rx;
+    uint64_t rx_len;
+    uint32_t nseg;
+    // The caller will unmask d_rx right after the scan (a step).  On the
+    // checked paths the unmask is then queued before the host waits for the
+    // device's check -- a rejected table has a zero count, so that unmask
+    // does nothing -- and `unmasked` reports whether it stands.
+    uint8_t* unmask_into;
+    scan_scratch sc;
+    dspec_status* status_d = nullptr;         // the pinned status, device-mapped
+    const dspec_status* status_h = nullptr;   // ... and as the host reads it
+    int up_slot = -1;                // upload slot the first pass frees (-1: none, or freed)
+    uint64_t tile = 0, ntiles = 0;   // k_unmask geometry of the batch
+    uint64_t bound = 0;              // record bound of the batch
+    uint64_t nfr = 0;                // its records: the bound until a count has been read
+    bool tiles_done = false;         // the tile kernels are queued
+    bool unmasked = false;
+};
+
+// The current table set's scratch arrays and the upload the first pass reads.
+scan_scratch scratch_of(hvws_ctx* c) {
+    scan_scratch sc;
+    sc.mid = c->T().sc_mid.as<dmid>();
+    sc.npred = c->T().sc_npred.as<uint64_t>();
+    sc.pbase = c->T().sc_pbase.as<uint64_t>();
+    sc.first_fail = c->T().sc_fail.as<uint64_t>();
+    sc.last_masked = c->T().sc_masked.as<uint64_t>();
+    sc.total_pred = c->T().sc_total.as<uint64_t>();
+    sc.est = c->T().sc_est.as<uint64_t>();
+    sc.src_segs = c->up_src_segs;
+    sc.src_carry = c->up_src_carry;
+    sc.segs_w = c->segs.as<dseg>();
+    sc.carry_w = c->carry_in.as<dcarry>();
+    return sc;
+}
+
+// One pass of launch_scan.  After the first the device tables hold the
+// uploaded segments; the pinned slot is free once its first kernel has run.
+hipError_t issue_pass(scan_job& j, int which) {
+    hvws_ctx* c = j.c;
+    hipError_t e = launch_scan(which, j.d_rx, j.rx_len, c->segs.as<dseg>(), j.nseg, c->carry_in.as<dcarry>(),
+                               c->T().carry_out.as<dcarry>(), c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(),
+                               c->T().total.as<uint64_t>(), j.sc, frames_of(c), c->vmask, c->cs);
+    j.sc.src_segs = nullptr;
+    j.sc.src_carry = nullptr;
+    if (e != hipSuccess || j.up_slot < 0) return e;
+    e = hipEventRecord(c->up_ev[j.up_slot], c->cs);
+    c->up_pending[j.up_slot] = e == hipSuccess;
+    j.up_slot = -1;
+    return e;
+}
+
+// The device's verdict for the pass just issued (after a wait on the stream
+// or for the published status): the record count into j.nfr, the SPEC_* flags.
+int read_status(scan_job& j, uint32_t& flags) {
+    const dspec_status* st = j.status_h;
+    if (st->seq != j.sc.seq) return set_err(HVWS_EHIP, "scan status not published (seq %llu, want %llu)",
+                                            (unsigned long long)st->seq, (unsigned long long)j.sc.seq);
+    j.nfr = st->total;
+    flags = st->flags;
+    if (flags & SPEC_ERR) return set_err(HVWS_EHIP, "scan check reported an error (seq %llu)",
+                                         (unsigned long long)j.sc.seq);
+    if (j.nfr >= 0xFFFFFFF0ull)
+        return set_err(HVWS_EINVAL, "batch holds %llu frames (max 2^32-16)", (unsigned long long)j.nfr);
+    return HVWS_OK;
+}
+
+// A rejected check in pipelined mode.  The speculative unmask was queued
+// on c->stream, behind the previous batch's unmask, and reads this set's
+// tile index and count when it runs, not when it was queued.  The exact
+// re-scan rewrites those tables on c->cs; unordered, a still-waiting
+// speculative unmask would see the re-scan's tiles and XOR for real, and
+// the caller's unmask would then XOR the payloads back.  So the re-scan
+// waits for it (the set's free event, recorded right after it).
+int join_rejected(const scan_job& j) {
+    hvws_ctx* c = j.c;
+    if (j.unmask_into && c->cs != c->stream) HIP_OR(hipStreamWaitEvent(c->cs, c->T().free_wait, 0), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int queue_tiles(const scan_job& j) {
+    hvws_ctx* c = j.c;
+    HIP_OR(launch_unmask_tiles(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), c->T().f_keyrot.as<uint32_t>(),
+                               c->T().total.as<uint64_t>(), c->T().tile_first.as<uint32_t>(),
+                               c->T().tile_key.as<uint32_t>(), c->T().tile_kind.as<uint8_t>(), j.ntiles, j.tile, j.rx_len,
+                               c->cs),
+           HVWS_EHIP);
+    return HVWS_OK;
+}
+
+// One checked attempt: a pass whose table the device checks, with the tile
+// kernels and the step's unmask queued before the host waits for the verdict,
+// so the device runs on instead of idling through a host round trip.
+// `which` is SCAN_SPEC, SCAN_SLACK, or SCAN_SINGLE for the capacity check of
+// a one-segment pass that is already queued.  Accepted: j.tiles_done (and
+// j.unmasked for a step).  Rejected: the count is zero on the device, so what
+// was queued does nothing, and the re-scan is ordered behind it (join_rejected).
+int checked_attempt(scan_job& j, int which, uint32_t& flags) {
+    hvws_ctx* c = j.c;
+    int rc;
+    j.sc.seq = ++c->scan_seq;
+    if (which == SCAN_SINGLE) {
+        HIP_OR(launch_cap_check(c->T().total.as<uint64_t>(), c->T().frame_cap, j.status_d, j.sc.seq, c->cs), HVWS_EHIP);
+    } else {
+        // a set not used yet gets the other set's capacity (the table must
+        // hold the batch for the check to pass: the last count, with room)
+        const uint64_t other = c->ts[c->cur ^ 1].frame_cap;
+        if (c->T().frame_cap < other) HIP_OR(ensure_frames(c, other, /*exact=*/true), HVWS_ENOMEM);
+        j.sc.no_verify = (c->verify_mode < 0 ? c->verify_hint : c->verify_mode != 0) ? 0u : 1u;
+        HIP_OR(issue_pass(j, which), HVWS_EHIP);
+    }
+    if ((rc = queue_tiles(j)) != HVWS_OK) return rc;
+    // Pipelined SPEC: the host waits for the scan's last kernel (it runs
+    // beside the previous unmask) and then queues this unmask with no
+    // cross-stream wait packet between the two unmasks.  Otherwise the
+    // unmask is queued behind the check at once.
+    const bool ordered = which == SCAN_SPEC && j.unmask_into && c->cs != c->stream;
+    if (ordered) {
+        HIP_OR(launch_publish_tiles(j.status_d, j.sc.seq, c->cs), HVWS_EHIP);
+    } else if (j.unmask_into) {
+        HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
+        HIP_OR(issue_unmask(c, j.unmask_into, j.rx_len), HVWS_EHIP);
+    }
+    if ((rc = wait_status(c, j.sc.seq)) != HVWS_OK) return rc;
+    if ((rc = read_status(j, flags)) != HVWS_OK) return rc;
+    const bool ok = (flags & SPEC_OK) != 0;
+    if (which != SCAN_SINGLE) c->verify_hint = j.status_h->long_run_seen != 0;
+    if (which == SCAN_SPEC) c->spec_ok = ok;   // before the unmask below: issue_unmask picks its pieces by it
+    if (!ok) return join_rejected(j);
+    if (ordered) {
+        if ((rc = wait_status(c, j.sc.seq, /*tiles=*/true)) != HVWS_OK) return rc;
+        HIP_OR(issue_unmask(c, j.unmask_into, j.rx_len, /*joined=*/true), HVWS_EHIP);
+    }
+    j.tiles_done = true;
+    j.unmasked = j.unmask_into != nullptr;
+    return HVWS_OK;
+}
+
+// A long one-segment batch is sieved (parallel discovery) unless the last
+// sieved scan found uniform sizes: then 15 scans walk before the next try.
+// Sets j.sc.sieve = &svb when this scan sieves.  Results never depend on it.
+int choose_sieve(scan_job& j, sieve_bufs& svb) {
+    hvws_ctx* c = j.c;
+    if (c->sv_gen != sieve_generation()) {
+        c->sv_gen = sieve_generation();
+        c->sv_skip = 0;
+        c->sv_ran = false;
+        c->sv_hint_pre = c->sv_hint_surv = 0;
+        c->sv_win_len = 0;
+        c->sv_full_left = 0;
+        c->sv_hint_win = false;
+        c->sv_mean = 0;
+    }
+    if (j.rx_len < sieve_min()) return HVWS_OK;
+    if (sieve_state_ready(c) && c->h_sv.as<dsieve>()->active == 0 && c->sv_skip == 0) c->sv_skip = 15;
+    if (c->sv_skip) {
+        --c->sv_skip;
+        c->sv_ran = false;
+        return HVWS_OK;
+    }
+    HIP_OR(c->h_sv.ensure(sizeof(dsieve) + 32), HVWS_ENOMEM);
+    if (!c->sv_ev) HIP_OR(hipEventCreateWithFlags(&c->sv_ev, hipEventDisableTiming), HVWS_EHIP);
+    // no room for the sieve's tables (ensure_sieve released them): walk instead
+    c->sv_ran = ensure_sieve(c, j.rx_len, svb) == HVWS_OK;
+    if (c->sv_ran) j.sc.sieve = &svb;
+    return HVWS_OK;
+}
+
+// One stream: its base is 0, so EMIT needs no COUNT walk (a mixed-size
+// stream's serial walk runs once).  The table is sized by the bound when that
+// is small, else by an estimate (1.25 x the last one-stream count, at least
+// 2^20 records) that is checked after the pass and re-emitted into an
+// exact-size table if it overflowed.  (Sizing by the bound would give a
+// 256 MiB chunk of 64 KiB frames a 3.2 GB table for its ~4000 records.)
+int scan_single(scan_job& j) {
+    hvws_ctx* c = j.c;
+    int rc;
+    c->scan_path = HVWS_PATH_SINGLE;
+    const uint64_t guess = std::max<uint64_t>(kSingleMin, c->single_hint + c->single_hint / 4);
+    HIP_OR(ensure_frames(c, std::min<uint64_t>(j.bound, guess)), HVWS_ENOMEM);
+    sieve_bufs svb;
+    if ((rc = choose_sieve(j, svb)) != HVWS_OK) return rc;
+    HIP_OR(issue_pass(j, SCAN_SINGLE), HVWS_EHIP);
+    if (j.bound > c->T().frame_cap) {
+        // The table was sized by an estimate: the device checks the count
+        // against it (over capacity zeroes the count) and publishes it.
+        uint32_t flags = 0;
+        if ((rc = checked_attempt(j, SCAN_SINGLE, flags)) != HVWS_OK) return rc;
+        if (!j.tiles_done) {   // overflowed: re-emit into an exact table (the caller unmasks)
+            HIP_OR(ensure_frames(c, j.nfr + 1), HVWS_ENOMEM);
+            HIP_OR(issue_pass(j, SCAN_EMIT), HVWS_EHIP);
+            HIP_OR(launch_offsets(c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), 1,
+                                  c->T().total.as<uint64_t>(), c->cs),
+                   HVWS_EHIP);
+        }
+        c->nfr_known = true;
+        c->single_hint = j.nfr;
+    }
+    if (c->sv_ran) {   // state and counts for the next scan's choices and hvws_last_sieve
+        HIP_OR(hipMemcpyAsync(c->h_sv.p, c->sv_state.p, sizeof(dsieve), hipMemcpyDeviceToHost, c->cs), HVWS_EHIP);
+        HIP_OR(hipMemcpyAsync(c->h_sv.as<uint8_t>() + sizeof(dsieve), c->sv_cnt.p, 32, hipMemcpyDeviceToHost, c->cs),
+               HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->sv_ev, c->cs), HVWS_EHIP);
+    }
+    j.sc.sieve = nullptr;
+    return HVWS_OK;
+}
+
+// Frame records are bounded: after a segment's first record every frame
+// spends >= 2 of its bytes.  When the bound fits the table, EMIT follows
+// COUNT with no host round trip and the count stays on the device (the
+// tile kernels and k_unmask read it there).
+int scan_bounded(scan_job& j) {
+    hvws_ctx* c = j.c;
+    c->scan_path = HVWS_PATH_COUNT_EMIT;
+    HIP_OR(issue_pass(j, SCAN_COUNT), HVWS_EHIP);
+    HIP_OR(ensure_frames(c, j.bound), HVWS_ENOMEM);
+    HIP_OR(issue_pass(j, SCAN_EMIT), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+// Large batch: does this one take the RUN path?  A step's batch of small
+// uniform frames (the last exact or SPEC scan matched the uniform estimates):
+// discovery is k_head alone, the unmask checks every header it loads
+// (hvws_internal.h, drun).  Segments of RUN_MIN_SEG bytes or more on average:
+// k_unmask_run takes two segments per tile and leaves any between to the repair.
+bool run_chosen(scan_job& j) {
+    hvws_ctx* c = j.c;
+    // The last RUN verdict the device has published: a failed hypothesis
+    // turns RUN off for the next 16 steps and the next scan exact.
+    const uint64_t vseq = __atomic_load_n(&j.status_h->run_seq, __ATOMIC_ACQUIRE);
+    if (vseq != c->run_seen) {
+        c->run_seen = vseq;
+        if (j.status_h->run_failed) {
+            c->run_skip = 16;
+            c->spec_ok = false;
+        }
+    }
+    const bool run_auto = c->run_mode < 0 && c->spec_ok && c->spec_mode != 0 && !c->run_skip && c->last_mean &&
+                          c->last_mean <= RUN_MAX_FRAME && j.rx_len / j.nseg >= RUN_MIN_SEG && run_env();
+    if (c->run_skip && !c->materializing) --c->run_skip;
+    return j.unmask_into && c->run_call && c->vmask == 0 && (run_auto || c->run_mode == 1);
+}
+
+// RUN: run descriptors and the tile-segment index, then the unmask at once.
+// No frame table, no count (finish_scan skips what needs them).
+int scan_run(scan_job& j) {
+    hvws_ctx* c = j.c;
+    c->scan_path = HVWS_PATH_RUN;
+    HIP_OR(c->T().runs.ensure((uint64_t)j.nseg * sizeof(drun) + 64), HVWS_ENOMEM);
+    HIP_OR(c->T().run_fail.ensure_zeroed((uint64_t)j.nseg * 4 + 64, c->cs), HVWS_ENOMEM);
+    j.sc.run_tile = RUN_TILE;
+    j.sc.run_ntiles = (j.rx_len + RUN_TILE - 1) / RUN_TILE;
+    HIP_OR(c->T().run_trun.ensure((j.sc.run_ntiles + 1) * sizeof(dtrun)), HVWS_ENOMEM);
+    j.sc.runs = c->T().runs.as<drun>();
+    j.sc.run_fail = c->T().run_fail.as<uint32_t>();
+    j.sc.run_trun = c->T().run_trun.as<dtrun>();
+    HIP_OR(issue_pass(j, SCAN_RUN), HVWS_EHIP);
+    c->run_seq = ++c->scan_seq;
+    c->run_active = true;
+    c->nseg = j.nseg;   // issue_unmask reads it
+    if (c->cs != c->stream) {   // pipelined: host-ordered, as SPEC (checked_attempt)
+        HIP_OR(launch_publish_tiles(j.status_d, c->run_seq, c->cs), HVWS_EHIP);
+        if (int rc = wait_status(c, c->run_seq, /*tiles=*/true)) return rc;
+        HIP_OR(issue_unmask(c, j.unmask_into, j.rx_len, /*joined=*/true), HVWS_EHIP);
+    } else {
+        HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
+        HIP_OR(issue_unmask(c, j.unmask_into, j.rx_len), HVWS_EHIP);
+    }
+    j.unmasked = true;
+    j.nfr = 0;
+    return HVWS_OK;
+}
+
+// SLACK's scratch table for this batch, if SLACK is to be tried: cap_seg
+// records per segment region (1.5 x the last exact scan's largest segment).
+// A scratch table that cannot be had is no error: scan exactly instead.
+bool slack_table_ready(const scan_job& j, uint64_t& cap_seg) {
+    hvws_ctx* c = j.c;
+    cap_seg = c->slack_seg + c->slack_seg / 2 + 16;
+    const uint64_t want = std::min<uint64_t>((uint64_t)j.nseg * cap_seg, j.bound) + 1;
+    if (c->spec_mode == 0 || c->spec_mode == 1 || !c->slack_seg || !(c->spec_mode == 2 || !c->spec_ok) ||
+        want > kSlackMaxRecords)
+        return false;
+    if (want <= c->sl_cap) return true;
+    const uint64_t n = want + want / 4;
+    dbuf* const tab[] = {&c->sl_hdr, &c->sl_off, &c->sl_len, &c->sl_length,   // 8 bytes per record
+                         &c->sl_key, &c->sl_keyrot, &c->sl_info};             // 4
+    bool ok = true;
+    for (int i = 0; i < 7; ++i) ok = ok && tab[i]->ensure(n * (i < 4 ? 8 : 4)) == hipSuccess;
+    c->sl_cap = ok ? n : 0;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (dbuf* b : tab) b->release();
+    }
+    return ok;
+}
+
+dframes slack_frames(hvws_ctx* c) {
+    return {c->sl_hdr.as<int64_t>(), c->sl_off.as<uint64_t>(), c->sl_len.as<uint64_t>(), c->sl_length.as<uint64_t>(),
+            c->sl_key.as<uint32_t>(), c->sl_keyrot.as<uint32_t>(), c->sl_info.as<uint32_t>(), c->sl_cap};
+}
+
+// Large batch: the table is sized from a count.  With the estimates holding
+// on the last batch, EMIT speculatively into the table as it is (SCAN_SPEC)
+// and let the device check it -- one walk, no host round trip before EMIT.
+// Mixed sizes: one EMIT walk into per-segment regions of a scratch table,
+// checked and compacted on the device (SCAN_SLACK); its check also tells
+// whether the uniform estimates held (SPEC next time).  Otherwise, or when
+// the check fails: COUNT, read the count, EMIT.
+int scan_large(scan_job& j) {
+    hvws_ctx* c = j.c;
+    int rc;
+    uint32_t flags = 0;
+    uint64_t cap_seg;
+    j.sc.status = j.status_d;
+    c->scan_path = HVWS_PATH_COUNT_READ_EMIT;
+    if ((c->spec_ok && c->spec_mode != 0) || c->spec_mode == 1) {
+        if ((rc = checked_attempt(j, SCAN_SPEC, flags)) != HVWS_OK) return rc;
+        c->scan_path = j.tiles_done ? HVWS_PATH_SPEC : HVWS_PATH_SPEC_FAILED;
+    }
+    if (!j.tiles_done && slack_table_ready(j, cap_seg)) {
+        HIP_OR(c->sl_bx.ensure((uint64_t)j.nseg * 16 + 16), HVWS_ENOMEM);
+        j.sc.slack = slack_frames(c);
+        j.sc.slack_cap = cap_seg;
+        j.sc.bases_x = c->sl_bx.as<uint64_t>();
+        j.sc.est_u = c->sl_bx.as<uint64_t>() + j.nseg + 1;
+        if ((rc = checked_attempt(j, SCAN_SLACK, flags)) != HVWS_OK) return rc;
+        if (j.tiles_done) {
+            c->slack_seg = j.status_h->max_seg_count;
+            c->spec_ok = (flags & SPEC_MATCH) != 0;   // uniform again: the next batch tries SPEC
+        }
+        c->scan_path = j.tiles_done ? HVWS_PATH_SLACK : HVWS_PATH_SLACK_FAILED;
+    }
+    if (!j.tiles_done) {
+        j.sc.seq = ++c->scan_seq;
+        j.sc.no_verify = 0;
+        HIP_OR(issue_pass(j, SCAN_COUNT), HVWS_EHIP);
+        HIP_OR(hipStreamSynchronize(c->cs), HVWS_EHIP);
+        if ((rc = read_status(j, flags)) != HVWS_OK) return rc;
+        c->verify_hint = j.status_h->long_run_seen != 0;
+        c->spec_ok = (flags & SPEC_MATCH) != 0;
+        c->slack_seg = j.status_h->max_seg_count;
+        HIP_OR(ensure_frames(c, j.nfr + 1), HVWS_ENOMEM);
+        HIP_OR(issue_pass(j, SCAN_EMIT), HVWS_EHIP);
+    }
+    c->nfr_known = true;
+    return HVWS_OK;
+}
+
+// Every path ends here.  A RUN scan left no frame table and has queued its
+// unmask: no tile kernels, no scan-end event, no table check, no count.
+int finish_scan(scan_job& j) {
+    hvws_ctx* c = j.c;
+    if (!c->run_active) {
+        int rc;
+        if (!j.tiles_done && (rc = queue_tiles(j)) != HVWS_OK) return rc;
+        if (!j.unmasked) HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
+        if (table_checks()) {   // the tile index's invariant (k_ends_check), tests only: one sync
+            HIP_OR(c->chk.ensure(8), HVWS_ENOMEM);
+            HIP_OR(c->h_chk.ensure(8), HVWS_ENOMEM);
+            HIP_OR(hipMemsetAsync(c->chk.p, 0, 8, c->cs), HVWS_EHIP);
+            HIP_OR(launch_ends_check(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
+                                     c->T().total.as<uint64_t>(), c->chk.as<unsigned long long>(), c->cs),
+                   HVWS_EHIP);
+            HIP_OR(hipMemcpyAsync(c->h_chk.p, c->chk.p, 8, hipMemcpyDeviceToHost, c->cs), HVWS_EHIP);
+            HIP_OR(hipStreamSynchronize(c->cs), HVWS_EHIP);
+            if (const uint64_t bad = *c->h_chk.as<uint64_t>())
+                return set_err(HVWS_EINVAL, "frame table: %llu record ends before its predecessor's (scan path %d)",
+                               (unsigned long long)bad, c->scan_path);
+        }
+    }
+    c->nseg = j.nseg;
+    c->nfr = j.nfr;
+    c->rx = j.d_rx;
+    c->rx_len = j.rx_len;
+    c->have_scan = true;
+    c->hcache_valid = false;
+    if (c->nfr_known && j.nfr) c->last_mean = j.rx_len / j.nfr;
+    return HVWS_OK;
+}
+
+// Discovery of one batch into the other table set: the preamble, the choice of
+// path (one function each, above), finish_scan.  unmask_into, unmasked: scan_job.
 int scan_device_carry(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, uint32_t nseg, uint8_t* unmask_into = nullptr,
                       bool* unmasked = nullptr) {
     if (unmasked) *unmasked = false;
@@ -694,415 +1069,45 @@ int scan_device_carry(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, uint32_
         HIP_OR(hipStreamWaitEvent(c->cs, c->T().free_wait, 0), HVWS_EHIP);
         c->T().free_pending = false;
     }
-    HIP_OR(c->T().counts.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().bases.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().total.ensure(8), HVWS_ENOMEM);
-    HIP_OR(c->T().carry_out.ensure((uint64_t)nseg * sizeof(dcarry) + 64), HVWS_ENOMEM);
+    tset& t = c->T();
+    for (dbuf* b : {&t.counts, &t.bases, &t.sc_npred, &t.sc_pbase, &t.sc_fail, &t.sc_masked, &t.sc_est})
+        HIP_OR(b->ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);   // one word per segment
+    HIP_OR(t.total.ensure(8), HVWS_ENOMEM);
+    HIP_OR(t.sc_total.ensure(8), HVWS_ENOMEM);
+    HIP_OR(t.carry_out.ensure((uint64_t)nseg * sizeof(dcarry) + 64), HVWS_ENOMEM);
+    HIP_OR(t.sc_mid.ensure((uint64_t)nseg * sizeof(dmid) + 64), HVWS_ENOMEM);
     HIP_OR(c->h_total.ensure(8), HVWS_ENOMEM);
-    HIP_OR(ensure_frames(c, 1), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_mid.ensure((uint64_t)nseg * sizeof(dmid) + 64), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_npred.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_pbase.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_fail.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_masked.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_total.ensure(8), HVWS_ENOMEM);
-    HIP_OR(c->T().sc_est.ensure((uint64_t)nseg * 8 + 8), HVWS_ENOMEM);
     HIP_OR(c->h_status.ensure(sizeof(dspec_status)), HVWS_ENOMEM);
-    scan_scratch sc;
-    sc.mid = c->T().sc_mid.as<dmid>();
-    sc.npred = c->T().sc_npred.as<uint64_t>();
-    sc.pbase = c->T().sc_pbase.as<uint64_t>();
-    sc.first_fail = c->T().sc_fail.as<uint64_t>();
-    sc.last_masked = c->T().sc_masked.as<uint64_t>();
-    sc.total_pred = c->T().sc_total.as<uint64_t>();
-    sc.est = c->T().sc_est.as<uint64_t>();
-    sc.src_segs = c->up_src_segs;
-    sc.src_carry = c->up_src_carry;
-    sc.segs_w = c->segs.as<dseg>();
-    sc.carry_w = c->carry_in.as<dcarry>();
-    sc.status = nullptr;
-    sc.seq = 0;
-    sc.sieve = nullptr;
-    sc.slack = frames_of(c);
-    sc.slack_cap = 0;
-    sc.bases_x = nullptr;
-    sc.est_u = nullptr;
-    sc.no_verify = 0;
-    sc.runs = nullptr;
-    sc.run_fail = nullptr;
-    sc.run_trun = nullptr;
-    sc.run_ntiles = sc.run_tile = 0;
-    dspec_status* status_d = mapped<dspec_status>(c->h_status);
-    const dspec_status* status_h = c->h_status.as<dspec_status>();
-    if (!status_d) return set_err(HVWS_EHIP, "pinned status not device-mapped");
-    const dseg* segs = c->segs.as<dseg>();
-    const dcarry* cin = c->carry_in.as<dcarry>();
+    HIP_OR(ensure_frames(c, 1), HVWS_ENOMEM);
+    scan_job j{c, d_rx, rx_len, nseg, unmask_into, scratch_of(c)};
+    j.status_d = mapped<dspec_status>(c->h_status);
+    j.status_h = c->h_status.as<dspec_status>();
+    if (!j.status_d) return set_err(HVWS_EHIP, "pinned status not device-mapped");
     // (run_materialize's rebuild of a RUN step's records keeps that step's
     // timing slot: no new slot, no events)
     if (!c->materializing) HIP_OR(begin_timed_scan(c), HVWS_EHIP);
-    // After the first pass the device tables hold the uploaded segments; the
-    // pinned slot is free once that pass's first kernel has run.
-    const int up_slot = c->up_slot;
+    j.up_slot = c->up_slot;
     c->up_slot = -1;
     c->up_src_segs = nullptr;
     c->up_src_carry = nullptr;
-    bool slot_released = up_slot < 0;
-    auto release_slot = [&]() -> hipError_t {
-        if (slot_released) return hipSuccess;
-        slot_released = true;
-        const hipError_t e2 = hipEventRecord(c->up_ev[up_slot], c->cs);
-        c->up_pending[up_slot] = e2 == hipSuccess;
-        return e2;
-    };
-    auto pass = [&](int which) {
-        const hipError_t e = launch_scan(which, d_rx, rx_len, segs, nseg, cin, c->T().carry_out.as<dcarry>(),
-                                         c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), c->T().total.as<uint64_t>(), sc,
-                                         frames_of(c), c->vmask, c->cs);
-        sc.src_segs = nullptr;
-        sc.src_carry = nullptr;
-        if (e == hipSuccess) return release_slot();
-        return e;
-    };
-    // k_spec_check's verdict for the pass just issued (after a wait on the
-    // stream or for the published status): the record count and the SPEC_* flags.
-    auto read_status = [&](uint64_t& n, uint32_t& flags) -> int {
-        if (status_h->seq != sc.seq) return set_err(HVWS_EHIP, "scan status not published (seq %llu, want %llu)",
-                                                    (unsigned long long)status_h->seq, (unsigned long long)sc.seq);
-        n = status_h->total;
-        flags = status_h->flags;
-        if (flags & SPEC_ERR) return set_err(HVWS_EHIP, "scan check reported an error (seq %llu)",
-                                             (unsigned long long)sc.seq);
-        if (n >= 0xFFFFFFF0ull)
-            return set_err(HVWS_EINVAL, "batch holds %llu frames (max 2^32-16)", (unsigned long long)n);
-        return HVWS_OK;
-    };
-    // A rejected check in pipelined mode.  The speculative unmask was queued
-    // on c->stream, behind the previous batch's unmask, and reads this set's
-    // tile index and count when it runs, not when it was queued.  The exact
-    // re-scan rewrites those tables on c->cs; unordered, a still-waiting
-    // speculative unmask would see the re-scan's tiles and XOR for real, and
-    // the caller's unmask would then XOR the payloads back.  So the re-scan
-    // waits for it (the set's free event, recorded right after it).
-    auto join_rejected = [&]() -> int {
-        if (unmask_into && c->cs != c->stream) HIP_OR(hipStreamWaitEvent(c->cs, c->T().free_wait, 0), HVWS_EHIP);
-        return HVWS_OK;
-    };
     c->variant = unmask_variant_for(rx_len);
-    const uint64_t tile = unmask_tile(c->variant);
-    const uint64_t ntiles = (rx_len + tile - 1) / tile;
-    HIP_OR(c->T().tile_first.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
-    HIP_OR(c->T().tile_key.ensure((ntiles + 2) * 4), HVWS_ENOMEM);
-    HIP_OR(c->T().tile_kind.ensure(ntiles + 16), HVWS_ENOMEM);
-    auto tiles = [&]() -> int {
-        HIP_OR(launch_unmask_tiles(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), c->T().f_keyrot.as<uint32_t>(),
-                                   c->T().total.as<uint64_t>(), c->T().tile_first.as<uint32_t>(), c->T().tile_key.as<uint32_t>(),
-                                   c->T().tile_kind.as<uint8_t>(), ntiles, tile, rx_len,
-                                   c->cs),
-               HVWS_EHIP);
-        return HVWS_OK;
-    };
-    // Frame records are bounded: after a segment's first record every frame
-    // spends >= 2 of its bytes.  When the bound fits the table, EMIT follows
-    // COUNT with no host round trip and the count stays on the device (the
-    // tile kernels and k_unmask read it there); otherwise read the count first.
-    const uint64_t bound = rx_len / 2 + 2 * (uint64_t)nseg + 1;
-    uint64_t nfr = bound;
+    j.tile = unmask_tile(c->variant);
+    j.ntiles = (rx_len + j.tile - 1) / j.tile;
+    HIP_OR(c->T().tile_first.ensure((j.ntiles + 8) * 4), HVWS_ENOMEM);
+    HIP_OR(c->T().tile_key.ensure((j.ntiles + 2) * 4), HVWS_ENOMEM);
+    HIP_OR(c->T().tile_kind.ensure(j.ntiles + 16), HVWS_ENOMEM);
+    j.nfr = j.bound = rx_len / 2 + 2 * (uint64_t)nseg + 1;
     c->nfr_known = false;
-    bool tiles_done = false;
-    if (nseg == 1) {
-        c->scan_path = HVWS_PATH_SINGLE;
-        // One stream: its base is 0, so EMIT needs no COUNT walk (a mixed-size
-        // stream's serial walk runs once).  The table is sized by the bound
-        // when that is small, else by an estimate (1.25 x the last one-stream
-        // count, at least 2^20 records) that is checked after the pass and
-        // re-emitted into an exact-size table if it overflowed.  (Sizing by
-        // the bound would give a 256 MiB chunk of 64 KiB frames a 3.2 GB
-        // table for its ~4000 records.)
-        const uint64_t guess = std::max<uint64_t>(kSingleMin, c->single_hint + c->single_hint / 4);
-        const uint64_t cap = std::min<uint64_t>(bound, guess);
-        HIP_OR(ensure_frames(c, cap), HVWS_ENOMEM);
-        // A long segment is sieved (parallel discovery) unless the last
-        // sieved scan found uniform sizes: then 15 scans walk before the next
-        // try.  Results never depend on it.
-        sieve_bufs svb;
-        if (c->sv_gen != sieve_generation()) {
-            c->sv_gen = sieve_generation();
-            c->sv_skip = 0;
-            c->sv_ran = false;
-            c->sv_hint_pre = c->sv_hint_surv = 0;
-            c->sv_win_len = 0;
-            c->sv_full_left = 0;
-            c->sv_hint_win = false;
-            c->sv_mean = 0;
-        }
-        if (rx_len >= sieve_min()) {
-            if (sieve_state_ready(c) && c->h_sv.as<dsieve>()->active == 0 && c->sv_skip == 0) c->sv_skip = 15;
-            if (c->sv_skip) {
-                --c->sv_skip;
-                c->sv_ran = false;
-            } else {
-                HIP_OR(c->h_sv.ensure(sizeof(dsieve) + 32), HVWS_ENOMEM);
-                if (!c->sv_ev) HIP_OR(hipEventCreateWithFlags(&c->sv_ev, hipEventDisableTiming), HVWS_EHIP);
-                if (ensure_sieve(c, rx_len, svb) == HVWS_OK) {
-                    sc.sieve = &svb;
-                    c->sv_ran = true;
-                } else {   // no room for the sieve's tables: walk instead (results are the same)
-                    (void)hipGetLastError();
-                    for (dbuf* b : {&c->sv_tcount, &c->sv_tbase, &c->sv_slot, &c->sv_pool, &c->sv_keep, &c->sv_kbase,
-                                    &c->sv_Spre, &c->sv_S,
-                                    &c->sv_J0, &c->sv_J1, &c->sv_mark, &c->sv_hops, &c->sv_rank, &c->sv_tmp, &c->sv_scr})
-                        b->release();
-                    c->sv_ran = false;
-                }
-            }
-        }
-        HIP_OR(pass(SCAN_SINGLE), HVWS_EHIP);
-        if (bound > c->T().frame_cap) {
-            // The table was sized by an estimate.  The device checks the count
-            // against it (over capacity zeroes the count, so the tile kernels
-            // and an unmask queued behind do nothing) and publishes it; the
-            // tiles and the unmask are queued before the host waits, so the
-            // device runs on instead of idling through a host round trip.
-            int rc;
-            uint32_t flags = 0;
-            sc.seq = ++c->scan_seq;
-            HIP_OR(launch_cap_check(c->T().total.as<uint64_t>(), c->T().frame_cap, status_d, sc.seq, c->cs), HVWS_EHIP);
-            if ((rc = tiles()) != HVWS_OK) return rc;
-            if (unmask_into) {
-                HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
-                HIP_OR(issue_unmask(c, unmask_into, rx_len), HVWS_EHIP);
-            }
-            if ((rc = wait_status(c, sc.seq)) != HVWS_OK) return rc;
-            if ((rc = read_status(nfr, flags)) != HVWS_OK) return rc;
-            if (flags & SPEC_OK) {
-                tiles_done = true;
-                if (unmask_into && unmasked) *unmasked = true;
-            } else {   // overflowed: re-emit into an exact table (the caller unmasks)
-                if ((rc = join_rejected()) != HVWS_OK) return rc;
-                HIP_OR(ensure_frames(c, nfr + 1), HVWS_ENOMEM);
-                HIP_OR(pass(SCAN_EMIT), HVWS_EHIP);
-                HIP_OR(launch_offsets(c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), 1,
-                                      c->T().total.as<uint64_t>(), c->cs),
-                       HVWS_EHIP);
-            }
-            c->nfr_known = true;
-            c->single_hint = nfr;
-        }
-        if (c->sv_ran) {   // state and counts for the next scan's choices and hvws_last_sieve
-            HIP_OR(hipMemcpyAsync(c->h_sv.p, c->sv_state.p, sizeof(dsieve), hipMemcpyDeviceToHost, c->cs), HVWS_EHIP);
-            HIP_OR(hipMemcpyAsync(c->h_sv.as<uint8_t>() + sizeof(dsieve), c->sv_cnt.p, 32, hipMemcpyDeviceToHost, c->cs),
-                   HVWS_EHIP);
-            HIP_OR(hipEventRecord(c->sv_ev, c->cs), HVWS_EHIP);
-        }
-        sc.sieve = nullptr;
-    } else if (bound <= (c->fast_bound ? c->fast_bound : kFastFrameBound)) {
-        c->scan_path = HVWS_PATH_COUNT_EMIT;
-        HIP_OR(pass(SCAN_COUNT), HVWS_EHIP);
-        HIP_OR(ensure_frames(c, bound), HVWS_ENOMEM);
-        HIP_OR(pass(SCAN_EMIT), HVWS_EHIP);
-    } else {
-        // Large batch: the table is sized from a count.  With the estimates
-        // holding on the last batch, EMIT speculatively into the table as
-        // it is (SCAN_SPEC) and let the device check it -- one walk, no
-        // host round trip before EMIT, and the tile kernels queued behind
-        // the check; the host then waits for the check only.  Otherwise (or
-        // when the check fails) COUNT, read the count, EMIT.
-        int rc;
-        uint32_t flags = 0;
-        sc.status = status_d;
-        bool done = false;
-        // The last RUN verdict the device has published: a failed hypothesis
-        // turns RUN off for the next 16 steps and the next scan exact.
-        const uint64_t vseq = __atomic_load_n(&status_h->pad3[0], __ATOMIC_ACQUIRE);
-        if (vseq != c->run_seen) {
-            c->run_seen = vseq;
-            if (status_h->pad3[1]) {
-                c->run_skip = 16;
-                c->spec_ok = false;
-            }
-        }
-        // RUN: a step's batch of small uniform frames (the last exact or SPEC
-        // scan matched the uniform estimates): discovery is k_head alone, the
-        // unmask checks every header it loads (hvws_internal.h, drun).
-        // Segments of RUN_MIN_SEG bytes or more on average: k_unmask_run
-        // takes two segments per tile and leaves any between to the repair.
-        const bool run_auto = c->run_mode < 0 && c->spec_ok && c->spec_mode != 0 && !c->run_skip && c->last_mean &&
-                              c->last_mean <= RUN_MAX_FRAME && rx_len / nseg >= RUN_MIN_SEG && run_env();
-        if (c->run_skip && !c->materializing) --c->run_skip;
-        if (unmask_into && c->run_call && c->vmask == 0 && (run_auto || c->run_mode == 1)) {
-            c->scan_path = HVWS_PATH_RUN;
-            HIP_OR(c->T().runs.ensure((uint64_t)nseg * sizeof(drun) + 64), HVWS_ENOMEM);
-            {
-                const void* was = c->T().run_fail.p;
-                const uint64_t had = c->T().run_fail.cap;
-                HIP_OR(c->T().run_fail.ensure((uint64_t)nseg * 4 + 64), HVWS_ENOMEM);
-                if (c->T().run_fail.p != was || c->T().run_fail.cap != had)
-                    HIP_OR(hipMemsetAsync(c->T().run_fail.p, 0, c->T().run_fail.cap, c->cs), HVWS_EHIP);
-            }
-            const uint64_t rtile = RUN_TILE;
-            const uint64_t rtiles = (rx_len + rtile - 1) / rtile;
-            HIP_OR(c->T().run_trun.ensure((rtiles + 1) * sizeof(dtrun)), HVWS_ENOMEM);
-            sc.runs = c->T().runs.as<drun>();
-            sc.run_fail = c->T().run_fail.as<uint32_t>();
-            sc.run_trun = c->T().run_trun.as<dtrun>();
-            sc.run_ntiles = rtiles;
-            sc.run_tile = rtile;
-            HIP_OR(pass(SCAN_RUN), HVWS_EHIP);
-            c->run_seq = ++c->scan_seq;
-            c->run_active = true;
-            c->nseg = nseg;
-            const bool ordered = c->cs != c->stream && host_order();
-            if (ordered) {
-                HIP_OR(launch_publish_tiles(status_d, c->run_seq, c->cs), HVWS_EHIP);
-                if ((rc = wait_status(c, c->run_seq, /*tiles=*/true)) != HVWS_OK) return rc;
-                HIP_OR(issue_unmask(c, unmask_into, rx_len, /*joined=*/true), HVWS_EHIP);
-            } else {
-                HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
-                HIP_OR(issue_unmask(c, unmask_into, rx_len), HVWS_EHIP);
-            }
-            if (unmasked) *unmasked = true;
-            c->nfr = 0;
-            c->nfr_known = false;
-            c->rx = d_rx;
-            c->rx_len = rx_len;
-            c->have_scan = true;
-            c->hcache_valid = false;
-            return HVWS_OK;
-        }
-        c->scan_path = HVWS_PATH_COUNT_READ_EMIT;
-        if ((c->spec_ok && c->spec_mode != 0) || c->spec_mode == 1) {
-            // a set not used yet gets the other set's capacity (the table
-            // must hold the estimated records for the check to pass)
-            if (c->T().frame_cap < c->ts[c->cur ^ 1].frame_cap)
-                HIP_OR(ensure_frames(c, c->ts[c->cur ^ 1].frame_cap, /*exact=*/true), HVWS_ENOMEM);
-            sc.seq = ++c->scan_seq;
-            sc.no_verify = (c->verify_mode < 0 ? c->verify_hint : c->verify_mode != 0) ? 0u : 1u;
-            HIP_OR(pass(SCAN_SPEC), HVWS_EHIP);
-            if ((rc = tiles()) != HVWS_OK) return rc;
-            // Pipelined: the host waits for the scan's last kernel (it runs
-            // beside the previous unmask) and then queues this unmask with no
-            // cross-stream wait packet between the two unmasks.  Otherwise
-            // the unmask is queued behind the check at once.
-            const bool ordered = unmask_into && c->cs != c->stream && host_order();
-            if (ordered) HIP_OR(launch_publish_tiles(status_d, sc.seq, c->cs), HVWS_EHIP);
-            if (unmask_into && !ordered) {
-                HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
-                HIP_OR(issue_unmask(c, unmask_into, rx_len), HVWS_EHIP);
-            }
-            if ((rc = wait_status(c, sc.seq)) != HVWS_OK) return rc;
-            if ((rc = read_status(nfr, flags)) != HVWS_OK) return rc;
-            c->verify_hint = status_h->pad2[1] != 0;
-            done = (flags & SPEC_OK) != 0;
-            c->spec_ok = done;
-            c->scan_path = done ? HVWS_PATH_SPEC : HVWS_PATH_SPEC_FAILED;
-            if (done && ordered) {
-                if ((rc = wait_status(c, sc.seq, /*tiles=*/true)) != HVWS_OK) return rc;
-                HIP_OR(issue_unmask(c, unmask_into, rx_len, /*joined=*/true), HVWS_EHIP);
-            }
-            if (done && unmask_into && unmasked) *unmasked = true;
-            if (!done && (rc = join_rejected()) != HVWS_OK) return rc;
-            tiles_done = done;
-        }
-        // Mixed sizes: one EMIT walk into per-segment regions of a scratch
-        // table, checked and compacted on the device (SCAN_SLACK).  Its check
-        // also tells whether the uniform estimates held (SPEC next time).
-        const uint64_t cap_seg = c->slack_seg + c->slack_seg / 2 + 16;
-        const uint64_t want = std::min<uint64_t>((uint64_t)nseg * cap_seg, bound) + 1;
-        bool slack_try = !done && c->spec_mode != 0 && c->spec_mode != 1 && c->slack_seg &&
-                         (c->spec_mode == 2 || !c->spec_ok) && want <= kSlackMaxRecords;
-        if (slack_try && want > c->sl_cap) {
-            // a scratch table that cannot be had is no error: scan exactly instead
-            const uint64_t n = want + want / 4;
-            bool ok = true;
-            for (dbuf* b : {&c->sl_hdr, &c->sl_off, &c->sl_len, &c->sl_length}) ok = ok && b->ensure(n * 8) == hipSuccess;
-            for (dbuf* b : {&c->sl_key, &c->sl_keyrot, &c->sl_info}) ok = ok && b->ensure(n * 4) == hipSuccess;
-            c->sl_cap = ok ? n : 0;
-            if (!ok) {
-                (void)hipGetLastError();
-                for (dbuf* b : {&c->sl_hdr, &c->sl_off, &c->sl_len, &c->sl_length, &c->sl_key, &c->sl_keyrot,
-                                &c->sl_info})
-                    b->release();
-            }
-            slack_try = ok;
-        }
-        if (slack_try) {
-            HIP_OR(c->sl_bx.ensure((uint64_t)nseg * 16 + 16), HVWS_ENOMEM);
-            // the frame table must hold the batch: the last count, with room
-            if (c->T().frame_cap < c->ts[c->cur ^ 1].frame_cap)
-                HIP_OR(ensure_frames(c, c->ts[c->cur ^ 1].frame_cap, /*exact=*/true), HVWS_ENOMEM);
-            sc.slack.hdr_off = c->sl_hdr.as<int64_t>();
-            sc.slack.pay_off = c->sl_off.as<uint64_t>();
-            sc.slack.pay_len = c->sl_len.as<uint64_t>();
-            sc.slack.length = c->sl_length.as<uint64_t>();
-            sc.slack.key = c->sl_key.as<uint32_t>();
-            sc.slack.keyrot = c->sl_keyrot.as<uint32_t>();
-            sc.slack.info = c->sl_info.as<uint32_t>();
-            sc.slack.cap = c->sl_cap;
-            sc.slack_cap = cap_seg;
-            sc.bases_x = c->sl_bx.as<uint64_t>();
-            sc.est_u = c->sl_bx.as<uint64_t>() + nseg + 1;
-            sc.seq = ++c->scan_seq;
-            sc.no_verify = (c->verify_mode < 0 ? c->verify_hint : c->verify_mode != 0) ? 0u : 1u;
-            HIP_OR(pass(SCAN_SLACK), HVWS_EHIP);
-            if ((rc = tiles()) != HVWS_OK) return rc;
-            if (unmask_into) {
-                HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
-                HIP_OR(issue_unmask(c, unmask_into, rx_len), HVWS_EHIP);
-            }
-            if ((rc = wait_status(c, sc.seq)) != HVWS_OK) return rc;
-            if ((rc = read_status(nfr, flags)) != HVWS_OK) return rc;
-            c->verify_hint = status_h->pad2[1] != 0;
-            done = (flags & SPEC_OK) != 0;
-            if (done) {
-                c->slack_seg = status_h->pad2[0];
-                c->spec_ok = (flags & SPEC_MATCH) != 0;   // uniform again: the next batch tries SPEC
-                if (unmask_into && unmasked) *unmasked = true;
-            } else if ((rc = join_rejected()) != HVWS_OK) {
-                return rc;
-            }
-            c->scan_path = done ? HVWS_PATH_SLACK : HVWS_PATH_SLACK_FAILED;
-            tiles_done = done;
-        }
-        if (!done) {
-            sc.seq = ++c->scan_seq;
-            sc.no_verify = 0;
-            HIP_OR(pass(SCAN_COUNT), HVWS_EHIP);
-            HIP_OR(hipStreamSynchronize(c->cs), HVWS_EHIP);
-            if ((rc = read_status(nfr, flags)) != HVWS_OK) return rc;
-            c->verify_hint = status_h->pad2[1] != 0;
-            c->spec_ok = (flags & SPEC_MATCH) != 0;
-            c->slack_seg = status_h->pad2[0];
-            HIP_OR(ensure_frames(c, nfr + 1), HVWS_ENOMEM);
-            HIP_OR(pass(SCAN_EMIT), HVWS_EHIP);
-        }
-        c->nfr_known = true;
-    }
-    if (!tiles_done) {
-        int rc = tiles();
-        if (rc) return rc;
-    }
-    if (!(unmasked && *unmasked)) HIP_OR(tev_record(c, 1, c->cs), HVWS_EHIP);
-    if (table_checks()) {   // the tile index's invariant (k_ends_check), tests only: one sync
-        HIP_OR(c->chk.ensure(8), HVWS_ENOMEM);
-        HIP_OR(c->h_chk.ensure(8), HVWS_ENOMEM);
-        HIP_OR(hipMemsetAsync(c->chk.p, 0, 8, c->cs), HVWS_EHIP);
-        HIP_OR(launch_ends_check(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), c->T().total.as<uint64_t>(),
-                                 c->chk.as<unsigned long long>(), c->cs),
-               HVWS_EHIP);
-        HIP_OR(hipMemcpyAsync(c->h_chk.p, c->chk.p, 8, hipMemcpyDeviceToHost, c->cs), HVWS_EHIP);
-        HIP_OR(hipStreamSynchronize(c->cs), HVWS_EHIP);
-        if (const uint64_t bad = *c->h_chk.as<uint64_t>())
-            return set_err(HVWS_EINVAL, "frame table: %llu record ends before its predecessor's (scan path %d)",
-                           (unsigned long long)bad, c->scan_path);
-    }
-    c->nseg = nseg;
-    c->nfr = nfr;
-    c->rx = d_rx;
-    c->rx_len = rx_len;
-    c->have_scan = true;
-    c->hcache_valid = false;
-    if (c->nfr_known && nfr) c->last_mean = rx_len / nfr;
-    return HVWS_OK;
+    int rc;
+    if (nseg == 1)
+        rc = scan_single(j);
+    else if (j.bound <= (c->fast_bound ? c->fast_bound : kFastFrameBound))
+        rc = scan_bounded(j);
+    else   // the table is sized from a count, or (RUN) not built at all
+        rc = run_chosen(j) ? scan_run(j) : scan_large(j);
+    if (rc == HVWS_OK) rc = finish_scan(j);
+    if (unmasked) *unmasked = j.unmasked;
+    return rc;
 }
 
 // The records of a RUN step, built when a reader asks for them: an exact scan
@@ -2523,10 +2528,8 @@ int hvws_debug_stall(hvws_ctx* c, uint32_t usec) {
 
 int hvws_scan(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, const hvws_segment* segs,
               const websocket_parser* carry_in, uint32_t nseg) {
-    int rc = check_ctx(c);
+    int rc = check_batch_args(c, d_rx, segs, nseg);
     if (rc) return rc;
-    if (!segs && nseg) return set_err(HVWS_EINVAL, "null segment table");
-    if (((uintptr_t)d_rx & 15u) != 0) return set_err(HVWS_EINVAL, "rx buffer must be 16-byte aligned");
     if ((rc = upload_segments(c, segs, carry_in, nseg, rx_len)) != HVWS_OK) return rc;
     return scan_device_carry(c, d_rx, rx_len, nseg);
 }
@@ -2549,13 +2552,7 @@ int hvws_utf8(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, con
     const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
     const uint64_t ntiles = (rx_len + U8_TILE - 1) / U8_TILE;
     HIP_OR(c->u8_words.ensure(cap * 4 + 16), HVWS_ENOMEM);
-    {
-        const void* was = c->u8_flags.p;
-        const uint64_t had = c->u8_flags.cap;
-        HIP_OR(c->u8_flags.ensure(cap * 4 + 16), HVWS_ENOMEM);
-        if (c->u8_flags.p != was || c->u8_flags.cap != had)
-            HIP_OR(hipMemsetAsync(c->u8_flags.p, 0, c->u8_flags.cap, c->stream), HVWS_EHIP);
-    }
+    HIP_OR(c->u8_flags.ensure_zeroed(cap * 4 + 16, c->stream), HVWS_ENOMEM);
     HIP_OR(c->u8_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
     HIP_OR(c->u8_meta.ensure(64), HVWS_ENOMEM);
     HIP_OR(c->u8_in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
@@ -2642,10 +2639,8 @@ uint64_t hvws_utf8_tile(void) { return U8_TILE; }
 
 int hvws_step_resident(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, const hvws_segment* segs,
                        const websocket_parser* carry_in, uint32_t nseg) {
-    int rc = check_ctx(c);
+    int rc = check_batch_args(c, d_rx, segs, nseg);
     if (rc) return rc;
-    if (!segs && nseg) return set_err(HVWS_EINVAL, "null segment table");
-    if (((uintptr_t)d_rx & 15u) != 0) return set_err(HVWS_EINVAL, "rx buffer must be 16-byte aligned");
     if (!c->piped) {
         // Entering pipelined mode: both table sets may still be read by work
         // queued on the context stream.
@@ -2669,10 +2664,8 @@ int hvws_step_resident(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, const hvws_s
 
 int hvws_step(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, const hvws_segment* segs,
               const websocket_parser* carry_in, uint32_t nseg) {
-    int rc = check_ctx(c);
+    int rc = check_batch_args(c, d_rx, segs, nseg);
     if (rc) return rc;
-    if (!segs && nseg) return set_err(HVWS_EINVAL, "null segment table");
-    if (((uintptr_t)d_rx & 15u) != 0) return set_err(HVWS_EINVAL, "rx buffer must be 16-byte aligned");
     if ((rc = upload_segments(c, segs, carry_in, nseg, rx_len)) != HVWS_OK) return rc;
     bool unmasked = false;
     c->run_call = true;
@@ -3259,7 +3252,7 @@ int64_t hvws_last_run_repairs(hvws_ctx* c) {
     if (check_ctx(c) != HVWS_OK || c->scan_path != HVWS_PATH_RUN) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
     const dspec_status* st = c->h_status.as<dspec_status>();
-    return __atomic_load_n(&st->pad3[0], __ATOMIC_ACQUIRE) == c->run_seq ? (int64_t)st->pad3[1] : -1;
+    return __atomic_load_n(&st->run_seq, __ATOMIC_ACQUIRE) == c->run_seq ? (int64_t)st->run_failed : -1;
 }
 
 int hvws_set_run(hvws_ctx* c, int mode) {

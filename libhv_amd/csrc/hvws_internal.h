@@ -126,10 +126,17 @@ struct dspec_status {
     uint64_t total;   // records of the batch (sum of the true counts)
     uint32_t flags;   // SPEC_*
     uint32_t pad;
-    uint64_t pad2[2];
+    uint64_t max_seg_count;   // largest segment count: sizes the next SLACK table
+    uint64_t long_run_seen;   // some segment had >= spec_min predicted frames (the next pass's verify hint)
     uint64_t tseq;    // seq again, published after the scan's last kernel (tile index complete)
-    uint64_t pad3[2];
+    uint64_t run_seq;      // RUN: the step whose repair pass published last (k_run_fix)
+    uint64_t run_failed;   // ... and its failed segments
 };
+static_assert(sizeof(dspec_status) == 64 && offsetof(dspec_status, seq) == 0 && offsetof(dspec_status, total) == 8 &&
+                  offsetof(dspec_status, flags) == 16 && offsetof(dspec_status, max_seg_count) == 24 &&
+                  offsetof(dspec_status, long_run_seen) == 32 && offsetof(dspec_status, tseq) == 40 &&
+                  offsetof(dspec_status, run_seq) == 48 && offsetof(dspec_status, run_failed) == 56,
+              "dspec_status layout: the host polls these words, the kernels store them");
 enum : uint32_t {
     SPEC_MATCH = 1u,   // every segment's record count equals k_head's estimate
     SPEC_OK = 2u,      // SCAN_SPEC: the speculative table is the exact table (match and within capacity)
@@ -195,7 +202,7 @@ hipError_t launch_run_tiles(const uint8_t* rx, uint64_t rx_len, const dseg* segs
 // The RUN unmask (RUN_TILE bytes per tile, the tiles k_run_tiles described)
 // and its repair pass; the timing events ride on the unmask's first dispatch
 // (start) and the repair's (stop).  The repair publishes (seq, failed
-// segments) to status->pad3 when it is done.
+// segments) to status->run_seq / run_failed when it is done.
 constexpr uint64_t RUN_TILE = 16384;   // 256 threads x 4 chunks of 16 B
 const char* run_kernel_name();
 hipError_t launch_unmask_run(uint8_t* rx, uint64_t rx_len, const drun* runs, const dtrun* trun, uint32_t nseg,
@@ -203,33 +210,33 @@ hipError_t launch_unmask_run(uint8_t* rx, uint64_t rx_len, const drun* runs, con
                              hipEvent_t ev_stop);
 constexpr uint64_t RUN_FAST_STRIDE = 1u << 20;   // run strides up to this take k_unmask_run's one-segment path
 
-struct scan_scratch {   // per-segment arrays (nseg entries) + one total
-    dmid*     mid;
-    uint64_t* npred;
-    uint64_t* pbase;
-    uint64_t* first_fail;
-    uint64_t* last_masked;   // 1 + index of the last masked verified frame, 0 none
-    uint64_t* total_pred;
-    uint64_t* est;           // records k_head predicts per segment (uniform-stride hypothesis)
+struct scan_scratch {   // host-side bundle for launch_scan: per-segment arrays (nseg entries) + one total
+    dmid*     mid = nullptr;
+    uint64_t* npred = nullptr;
+    uint64_t* pbase = nullptr;
+    uint64_t* first_fail = nullptr;
+    uint64_t* last_masked = nullptr;   // 1 + index of the last masked verified frame, 0 none
+    uint64_t* total_pred = nullptr;
+    uint64_t* est = nullptr;           // records k_head predicts per segment (uniform-stride hypothesis)
     // Zero-copy upload: when src_segs is set, the first k_head of the scan
     // reads the segment and carry tables from these (device-mapped pinned
     // host) arrays and writes the device tables the later kernels read.
-    const dseg*   src_segs;
-    const dcarry* src_carry;
-    dseg*         segs_w;
-    dcarry*       carry_w;
-    dspec_status* status;    // device-mapped pinned host
-    uint64_t      seq;
-    const sieve_bufs* sieve; // SINGLE / its re-EMIT: frame sieve buffers, nullptr = no sieve
-    dframes   slack;         // SLACK: scratch table
-    uint64_t  slack_cap;     // SLACK: records per segment region at most
-    uint64_t* bases_x;       // SLACK: exact bases (nseg)
-    uint64_t* est_u;         // SLACK: uniform-stride estimates (nseg), for SPEC_MATCH
-    uint32_t  no_verify;     // SPEC/SLACK: head + walk only (no k_verify pair, no k_head<true>)
-    drun*     runs;          // RUN: k_head writes each segment's run descriptor
-    uint32_t* run_fail;      // RUN: per-segment failure words + the batch's, zeroed by k_head / k_run_tiles
-    dtrun*    run_trun;      // RUN: per unmask tile (run_ntiles entries)
-    uint64_t  run_ntiles, run_tile;
+    const dseg*   src_segs = nullptr;
+    const dcarry* src_carry = nullptr;
+    dseg*         segs_w = nullptr;
+    dcarry*       carry_w = nullptr;
+    dspec_status* status = nullptr;    // device-mapped pinned host
+    uint64_t      seq = 0;
+    const sieve_bufs* sieve = nullptr; // SINGLE / its re-EMIT: frame sieve buffers, nullptr = no sieve
+    dframes   slack{};                 // SLACK: scratch table
+    uint64_t  slack_cap = 0;           // SLACK: records per segment region at most
+    uint64_t* bases_x = nullptr;       // SLACK: exact bases (nseg)
+    uint64_t* est_u = nullptr;         // SLACK: uniform-stride estimates (nseg), for SPEC_MATCH
+    uint32_t  no_verify = 0;           // SPEC/SLACK: head + walk only (no k_verify pair, no k_head<true>)
+    drun*     runs = nullptr;          // RUN: k_head writes each segment's run descriptor
+    uint32_t* run_fail = nullptr;      // RUN: per-segment failure words + the batch's, zeroed by k_head / k_run_tiles
+    dtrun*    run_trun = nullptr;      // RUN: per unmask tile (run_ntiles entries)
+    uint64_t  run_ntiles = 0, run_tile = 0;
 };
 
 // Bijective XCD-contiguous tile order: the dispatcher deals blocks b, b+8,

@@ -1658,8 +1658,8 @@ __device__ __forceinline__ void spec_check_body(const uint64_t* __restrict__ cou
             amax = s_max[w] > amax ? s_max[w] : amax;
             any_bad |= s_bad[w];
         }
-        status->pad2[0] = amax;   // largest segment count: sizes the next slack table
-        status->pad2[1] = (any_bad & 2u) ? 1u : 0u;   // some segment had >= spec_min predicted frames
+        status->max_seg_count = amax;   // largest segment count: sizes the next slack table
+        status->long_run_seen = (any_bad & 2u) ? 1u : 0u;   // some segment had >= spec_min predicted frames
         any_bad &= 1u;
         uint32_t flags = any_bad ? 0u : SPEC_MATCH;
         if (SPEC) {
@@ -1748,8 +1748,8 @@ __global__ __launch_bounds__(ONE_BLOCK) void k_slack_check(const uint64_t* __res
         *total = ok ? all : 0;
         status->total = all;
         status->flags = (ok ? SPEC_OK : 0u) | ((any_bad & 2u) ? 0u : SPEC_MATCH);
-        status->pad2[0] = amax;
-        status->pad2[1] = (any_bad & 4u) ? 1u : 0u;
+        status->max_seg_count = amax;
+        status->long_run_seen = (any_bad & 4u) ? 1u : 0u;
         __hip_atomic_store(&status->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -2642,8 +2642,8 @@ __global__ __launch_bounds__(256) void k_run_fix(uint8_t* __restrict__ rx, uint6
     const bool any = __hip_atomic_load(&fail[nseg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
     if (!any) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            status->pad3[1] = 0;
-            __hip_atomic_store(&status->pad3[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            status->run_failed = 0;
+            __hip_atomic_store(&status->run_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         return;
     }
@@ -2658,8 +2658,8 @@ __global__ __launch_bounds__(256) void k_run_fix(uint8_t* __restrict__ rx, uint6
     __syncthreads();
     if (s_last && threadIdx.x == 0) {
         __threadfence();
-        status->pad3[1] = __hip_atomic_load(&fail[nseg + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&status->pad3[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        status->run_failed = __hip_atomic_load(&fail[nseg + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&status->run_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         // the batch's words clean for this table set's next RUN step
         fail[nseg] = 0;
         fail[nseg + 1] = 0;
