@@ -20,6 +20,12 @@
  *                for a whole batch of outgoing frames at once.
  *   hvws_encode_keys  the handshake digest ws_encode_key (http/wsdef.c:11-20)
  *                for a batch of upgrade requests.
+ *   hvws_utf8    RFC 6455 sec. 8.1 over the batch's text messages (the
+ *                reference does not check it; opt-in).
+ *   hvws_messages  WebSocketParser::FeedRecvData's message reassembly
+ *                (http/WebSocketParser.cpp:8-75) for a whole batch: the
+ *                payload bytes with the headers squeezed out, unmasked on the
+ *                way, and the table of the messages they form -- on the device.
  *   hvws_wsp_*   C handle over the WebSocketParser class
  *                (http/WebSocketParser.h:19-31) for FFI callers.
  *
@@ -326,7 +332,8 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
 /* Device time (ms, HIP events on the ctx stream) of the last hvws_encode_keys
  * kernel, or of the last hvws_build_frames' device work after its size check
  * (tile index, source spans, k_build), or of the last hvws_utf8 (its tile
- * index and all three kernels) -- whichever was called last; the default
+ * index and all three kernels), or of the last hvws_messages (table pass,
+ * tile index and gather) -- whichever was called last; the default
  * build geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
 const char* hvws_build_kernel_name(void);
@@ -450,6 +457,100 @@ int64_t hvws_utf8_count(hvws_ctx* ctx);
 /* Bytes of the batch one workgroup of the word kernel covers (tests place
  * payload bytes around its multiples). */
 uint64_t hvws_utf8_tile(void);
+
+/* ---- message reassembly, device resident -------------------------------- */
+/* What WebSocketParser::FeedRecvData (http/WebSocketParser.cpp:8-75) delivers
+ * through onMessage, for every segment of a batch, without the bytes leaving
+ * the device.  Per connection the reference keeps a latched opcode and a
+ * growing message; over the frame records of a segment, in frame-table order,
+ * its rule (quirks of SURVEY.md Appendix A included) is:
+ *   - a record with HVWS_I_HDR whose opcode (info & 0xF) is non-zero latches
+ *     that opcode; a CONTINUE keeps the latch; a connection that has latched
+ *     nothing reports 8 (WS_OP_CLOSE, the constructor's value, Q6);
+ *   - the payload bytes of EVERY record are appended, whatever the opcode: a
+ *     control frame between two fragments lands in the message (Q5: text "AB"
+ *     not final, ping "PING", final continuation "CD" deliver (9, "ABPING") and
+ *     (9, "CD")); zero-length frames append nothing (Q7);
+ *   - a record with HVWS_I_END and FIN (info & 0x10) completes the message:
+ *     onMessage(latched opcode, bytes since the previous completion) fires and
+ *     the next record starts a new message.
+ *
+ * Output.  d_out receives the payload bytes of the batch with the headers
+ * squeezed out: record r's pay_len[r] bytes start at out_off[r] = the sum of
+ * pay_len[q] over q < r, so segments are in order and each segment's bytes
+ * are contiguous.  The message table holds pieces: a piece is the part of one
+ * message that lies in this batch.  Each FIN-ended record closes a piece; the
+ * records of a segment after its last FIN-ended one (all of its records when
+ * it has none) form one trailing open piece, possibly of 0 bytes.  Pieces are
+ * ordered by segment, then stream order; the table is dense.
+ *
+ * State.  An event loop keeps one hvws_msg_state per connection beside its
+ * websocket_parser carry: all zero at accept, state_in[s] on the way in,
+ * hvws_get_msg_state's on the way out.
+ *   - opcode out is the latch after the segment's last record;
+ *   - a segment with a FIN-ended record: open = 1 when records follow the last
+ *     such record, else 0; pending = the trailing piece's len (0 without one);
+ *   - a segment without one: open = state_in.open || it has records,
+ *     pending = state_in.pending + the segment's bytes;
+ *   - a segment without records returns its state unchanged and has no pieces;
+ *   - a state_in with open == 0 and pending != 0, or with opcode > 15, is
+ *     HVWS_EINVAL.
+ * Concatenating a message's pieces across batches is the caller's: the piece
+ * with HVWS_M_END gives the message's length in `total`. */
+typedef struct hvws_msg_state {   /* 16 B per connection; all zero = fresh */
+    uint64_t pending;             /* bytes of the open message delivered in earlier batches' pieces */
+    uint32_t opcode;              /* latched opcode, 0 = none latched yet */
+    uint32_t open;                /* 1 = a message is open (pieces without HVWS_M_END precede) */
+} hvws_msg_state;
+typedef struct hvws_msg {         /* 40 B */
+    uint64_t off, len;            /* the piece in d_out */
+    uint64_t total;               /* message bytes so far: pending carried in (first piece of the segment only) + len */
+    uint64_t rec;                 /* frame-table index of the piece's last record (joins hvws_utf8's bad[s]) */
+    uint32_t seg;
+    uint32_t info;                /* bits 0-3: opcode onMessage reports at that record; HVWS_M_END; HVWS_M_CONT */
+} hvws_msg;
+#define HVWS_M_END  (1u << 4)     /* a FIN frame ended here: the message is complete */
+#define HVWS_M_CONT (1u << 5)     /* first piece of a segment whose state_in.open was set */
+/* After hvws_scan / hvws_step[_resident] of d_rx (same buffer and length as
+ * the last scan, else HVWS_EINVAL; none before it: HVWS_EINVAL).  masked: 1 =
+ * payloads are still masked (after hvws_scan) and are XORed on the fly at each
+ * record's key and phase, records without a mask copied as they are -- the
+ * batch is never unmasked in place, receive-to-messages costs one read and one
+ * write of the payload; 0 = already unmasked (after a step).  d_rx is only
+ * read.  After a RUN step the frame records are built first (as for
+ * hvws_get_frames).  state_in: host, nseg entries, NULL = all fresh.
+ * Asynchronous on the ctx stream.  d_out must be 16-byte aligned and must not
+ * overlap [d_rx, d_rx + rx_len), else HVWS_EINVAL.  With out_cap >= rx_len the
+ * call does not wait (the payload cannot exceed the batch); with a smaller
+ * out_cap it waits once for the payload total and returns HVWS_EINVAL, nothing
+ * written, if that does not fit.  No byte of d_out at or beyond the payload
+ * total is ever written.  hvws_last_kernel_ms reports this pass when it was
+ * the last one called (the wait of a small out_cap included).  Results never
+ * depend on the scan path. */
+int hvws_messages(hvws_ctx* ctx, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
+                  const hvws_msg_state* state_in);
+/* Results of the last hvws_messages on ctx, valid until the next one; all but
+ * hvws_messages_device wait for it.  hvws_msg_count: its pieces (-1: none
+ * yet).  hvws_msg_bytes: the bytes it wrote to d_out.  hvws_get_messages:
+ * pieces first .. first + n - 1 (HVWS_EINVAL beyond the count).
+ * hvws_get_segment_messages: per segment its first piece and piece count
+ * (either may be NULL).  hvws_get_msg_state: per segment, the state to carry
+ * into the connection's next batch.  hvws_messages_device: the piece table in
+ * device memory, for a consumer kernel queued on the ctx stream (NULL: none
+ * yet); it reads hvws_msg_count entries, a number such a kernel takes from the
+ * host or bounds by the batch's record count. */
+int64_t hvws_msg_count(hvws_ctx* ctx);
+int hvws_msg_bytes(hvws_ctx* ctx, uint64_t* total);
+int hvws_get_messages(hvws_ctx* ctx, hvws_msg* out, uint64_t first, uint64_t n);
+int hvws_get_segment_messages(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+int hvws_get_msg_state(hvws_ctx* ctx, hvws_msg_state* out);
+const hvws_msg* hvws_messages_device(hvws_ctx* ctx);
+/* Output bytes one workgroup of the gather covers at most: it runs in one of
+ * two geometries, by the batch's mean bytes per record or $HVWS_EXPERIMENT
+ * msg = 0 / 1, and the smaller tile divides this one
+ * (tests place record boundaries around its multiples).  Results never depend
+ * on the geometry. */
+uint64_t hvws_msg_tile(void);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -71,6 +71,13 @@ FRAME_DTYPE = np.dtype(
     [("hdr_off", "<i8"), ("pay_off", "<u8"), ("pay_len", "<u8"), ("length", "<u8"), ("key", "<u4"), ("info", "<u4")]
 )
 assert FRAME_DTYPE.itemsize == ctypes.sizeof(Frame) == 40
+# hvws_msg / hvws_msg_state (include/hvws.h)
+MSG_DTYPE = np.dtype(
+    [("off", "<u8"), ("len", "<u8"), ("total", "<u8"), ("rec", "<u8"), ("seg", "<u4"), ("info", "<u4")]
+)
+MSG_STATE_DTYPE = np.dtype([("pending", "<u8"), ("opcode", "<u4"), ("open", "<u4")])
+assert MSG_DTYPE.itemsize == 40 and MSG_STATE_DTYPE.itemsize == 16
+MSG_END, MSG_CONT = 1 << 4, 1 << 5
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -154,6 +161,18 @@ _SIGS = {
     "hvws_get_utf8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_utf8_tile": (ctypes.c_uint64, []),
     "hvws_utf8_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_messages": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p],
+    ),
+    "hvws_msg_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_msg_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_get_messages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "hvws_get_segment_messages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_get_msg_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_messages_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_msg_tile": (ctypes.c_uint64, []),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -497,6 +516,46 @@ class Engine:
         bad = np.zeros(max(nseg, 1), dtype=np.uint64)
         _check(lib().hvws_get_utf8(self.ctx, st.ctypes.data, bad.ctypes.data), "hvws_get_utf8")
         return st[:nseg], bad[:nseg]
+
+    def messages(self, rx: DeviceBuffer, rx_len: int, masked: bool, out: DeviceBuffer, out_cap: int,
+                 state_in=None) -> None:
+        """hvws_messages over the last scan / step of rx: the payload bytes, headers
+        squeezed out (unmasked on the way when `masked`), into `out`, and the piece
+        table.  state_in: one MSG_STATE_DTYPE entry per segment (None = all fresh)."""
+        st = None
+        if state_in is not None:
+            st = np.ascontiguousarray(state_in, dtype=MSG_STATE_DTYPE)
+        _check(lib().hvws_messages(self.ctx, rx.ptr, rx_len, int(bool(masked)), out.ptr, out_cap,
+                                   st.ctypes.data if st is not None else None), "hvws_messages")
+
+    def message_table(self) -> np.ndarray:
+        """The pieces of the last messages() call (MSG_DTYPE)."""
+        n = lib().hvws_msg_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_msg_count")
+        out = np.zeros(n, dtype=MSG_DTYPE)
+        _check(lib().hvws_get_messages(self.ctx, out.ctypes.data, 0, n), "hvws_get_messages")
+        return out
+
+    def segment_messages(self, nseg: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(first piece, piece count) per segment of the last messages() call."""
+        first = np.zeros(max(nseg, 1), np.uint64)
+        cnt = np.zeros(max(nseg, 1), np.uint64)
+        _check(lib().hvws_get_segment_messages(self.ctx, first.ctypes.data, cnt.ctypes.data),
+               "hvws_get_segment_messages")
+        return first[:nseg], cnt[:nseg]
+
+    def msg_state(self, nseg: int) -> np.ndarray:
+        """Per segment, the state to carry into the connection's next batch (MSG_STATE_DTYPE)."""
+        out = np.zeros(max(nseg, 1), dtype=MSG_STATE_DTYPE)
+        _check(lib().hvws_get_msg_state(self.ctx, out.ctypes.data), "hvws_get_msg_state")
+        return out[:nseg]
+
+    def msg_bytes(self) -> int:
+        """Bytes the last messages() call wrote to its output."""
+        n = ctypes.c_uint64(0)
+        _check(lib().hvws_msg_bytes(self.ctx, ctypes.byref(n)), "hvws_msg_bytes")
+        return int(n.value)
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

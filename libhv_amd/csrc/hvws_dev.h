@@ -57,6 +57,149 @@ __device__ __forceinline__ void ld16(const uint8_t* rx, uint64_t rx_len, uint64_
     hi = sh ? (w1 >> sh) | (w2 << (64u - sh)) : w1;
 }
 
+// 16 bytes starting at arbitrary offset p of a buffer of plen bytes (bytes
+// past plen read 0; no load leaves the buffer).
+__device__ __forceinline__ void ld16_any(const uint8_t* pay, uint64_t plen, uint64_t p, uint64_t& lo, uint64_t& hi) {
+    const uint64_t a = p & ~15ull;
+    const uint32_t s = (uint32_t)(p & 15u);
+    if (a + 32 <= plen) {
+        const u32x4 va = *reinterpret_cast<const u32x4*>(pay + a);
+        const u32x4 vb = *reinterpret_cast<const u32x4*>(pay + a + 16);
+        const uint64_t w0 = va.x | ((uint64_t)va.y << 32), w1 = va.z | ((uint64_t)va.w << 32);
+        const uint64_t w2 = vb.x | ((uint64_t)vb.y << 32), w3 = vb.z | ((uint64_t)vb.w << 32);
+        const uint64_t x0 = s < 8 ? w0 : w1, x1 = s < 8 ? w1 : w2, x2 = s < 8 ? w2 : w3;
+        const uint32_t sh = (s & 7u) * 8u;
+        lo = sh ? (x0 >> sh) | (x1 << (64u - sh)) : x0;
+        hi = sh ? (x1 >> sh) | (x2 << (64u - sh)) : x1;
+    } else {
+        lo = hi = 0;
+        for (int b = 0; b < 16; ++b) {
+            const uint64_t q = p + b;
+            const uint64_t v = q < plen ? pay[q] : 0;
+            if (b < 8) lo |= v << (8 * b);
+            else hi |= v << (8 * (b - 8));
+        }
+    }
+}
+
+// bytes s..s+15 of the 32-byte little-endian pair (a, b), s in [0, 16)
+__device__ __forceinline__ u32x4 funnel16(u32x4 a, u32x4 b, uint32_t s) {
+    const uint64_t w0 = a.x | ((uint64_t)a.y << 32), w1 = a.z | ((uint64_t)a.w << 32);
+    const uint64_t w2 = b.x | ((uint64_t)b.y << 32), w3 = b.z | ((uint64_t)b.w << 32);
+    const uint64_t x0 = s < 8 ? w0 : w1, x1 = s < 8 ? w1 : w2, x2 = s < 8 ? w2 : w3;
+    const uint32_t sh = (s & 7u) * 8u;
+    const uint64_t lo = sh ? (x0 >> sh) | (x1 << (64u - sh)) : x0;
+    const uint64_t hi = sh ? (x1 >> sh) | (x2 << (64u - sh)) : x1;
+    return u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+}
+
+// OR bytes [0, b1 - b0) of the 16-byte little-endian value (vlo, vhi) into
+// bytes [b0, b1) of the chunk (olo, ohi); 0 <= b0 < b1 <= 16.
+__device__ __forceinline__ void put_bytes(uint64_t& olo, uint64_t& ohi, uint64_t vlo, uint64_t vhi, uint32_t b0,
+                                          uint32_t b1) {
+    const uint32_t n = b1 - b0;
+    if (n < 8) {
+        vlo &= ~0ull >> (64u - 8u * n);
+        vhi = 0;
+    } else if (n < 16) {
+        vhi = n == 8 ? 0 : vhi & (~0ull >> (64u - 8u * (n - 8u)));
+    }
+    if (b0 >= 8) {
+        vhi = vlo << (8u * (b0 - 8u));
+        vlo = 0;
+    } else if (b0) {
+        vhi = (vhi << (8u * b0)) | (vlo >> (64u - 8u * b0));
+        vlo <<= 8u * b0;
+    }
+    olo |= vlo;
+    ohi |= vhi;
+}
+
+// ---- device-wide exclusive scan (block scans, scan of the block sums, add) ----
+// Over any value type V whose V{} is the identity of an associative
+// scan_op(earlier, later): uint64_t sums here (the transmit side's frame
+// offsets, the sieve's ranks) and hvws_msg.hip's three-component records.
+// 256-thread workgroups, 4 consecutive elements per thread (1024 per block).
+// Workgroups of 1024 threads waited 125-200 us each for a CU with 16 free
+// wave slots while a pipelined unmask held the device (the frame sieve's
+// scans, profiles/r2o_raw), against ~5 us alone.
+constexpr int SCAN_T = 256;
+constexpr int SCAN_I = 4;
+constexpr int SCAN_B = SCAN_T * SCAN_I;
+
+__device__ __forceinline__ uint64_t scan_op(uint64_t a, uint64_t b) { return a + b; }
+
+template <typename V>
+struct scan_from_array {
+    const V* in;
+    __device__ __forceinline__ V operator()(uint64_t i) const { return in[i]; }
+};
+
+// out[i] = the scan of load(0 .. i - 1) within the element's block;
+// block_sums[b] = the block's total.
+template <typename V, typename LOAD>
+__global__ __launch_bounds__(SCAN_T) void k_scan_blocks(LOAD load, V* __restrict__ out, uint64_t n,
+                                                        V* __restrict__ block_sums, V* __restrict__ total_if_one) {
+    __shared__ V s[SCAN_T];
+    const uint32_t t = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)t * SCAN_I;
+    V v[SCAN_I], sum = V{};
+#pragma unroll
+    for (int k = 0; k < SCAN_I; ++k) {
+        v[k] = i0 + k < n ? load(i0 + k) : V{};
+        sum = scan_op(sum, v[k]);
+    }
+    s[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < SCAN_T; d <<= 1) {
+        const V a = t >= (unsigned)d ? s[t - d] : V{};
+        __syncthreads();
+        s[t] = scan_op(a, s[t]);
+        __syncthreads();
+    }
+    V run = t ? s[t - 1] : V{};   // exclusive within the block
+#pragma unroll
+    for (int k = 0; k < SCAN_I; ++k) {
+        if (i0 + k < n) out[i0 + k] = run;
+        run = scan_op(run, v[k]);
+    }
+    if (t == SCAN_T - 1) {
+        block_sums[blockIdx.x] = s[t];
+        if (total_if_one) *total_if_one = s[t];   // one block: its sum is the total
+    }
+}
+
+template <typename V>
+__global__ __launch_bounds__(SCAN_T) void k_add_block_base(V* __restrict__ out, uint64_t n,
+                                                           const V* __restrict__ block_base) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)threadIdx.x * SCAN_I;
+    const V b = block_base[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < SCAN_I; ++k)
+        if (i0 + k < n) out[i0 + k] = scan_op(b, out[i0 + k]);
+}
+
+// out[i] = scan of load(0 .. i - 1), *total = scan of all n; tmp holds
+// scan_tmp_words(n) values.  add_top = false leaves the last step to the
+// caller: out[i] is then relative to its block of SCAN_B elements, whose base
+// is tmp[ceil(n / SCAN_B) + i / SCAN_B] when n > SCAN_B (and V{} otherwise).
+constexpr uint64_t scan_tmp_words(uint64_t n) { return 4 * ((n + SCAN_B - 1) / SCAN_B) + 64; }
+template <typename V, typename LOAD>
+hipError_t launch_scan_of(LOAD load, V* out, uint64_t n, V* tmp, V* total, hipStream_t st, bool add_top = true) {
+    if (n == 0) return hipMemsetAsync(total, 0, sizeof(V), st);
+    const uint64_t nb = (n + SCAN_B - 1) / SCAN_B;
+    V* sums = tmp;
+    V* base = tmp + nb;
+    hipLaunchKernelGGL((k_scan_blocks<V, LOAD>), dim3((uint32_t)nb), dim3(SCAN_T), 0, st, load, out, n, sums,
+                       nb == 1 ? total : (V*)nullptr);
+    if (nb > 1) {
+        hipError_t e = launch_scan_of(scan_from_array<V>{sums}, base, nb, tmp + 2 * nb, total, st);
+        if (e != hipSuccess) return e;
+        if (add_top) hipLaunchKernelGGL((k_add_block_base<V>), dim3((uint32_t)nb), dim3(SCAN_T), 0, st, out, n, base);
+    }
+    return hipGetLastError();
+}
+
 struct hdr {
     uint64_t length;
     uint32_t hlen;

@@ -248,6 +248,15 @@ struct hvws_ctx {
     bool u8_up_pending = false;
     bool have_u8 = false;
     uint32_t u8_nseg = 0;
+    // hvws_messages: the scan's scratch, out_off per record, the tile index
+    // over the output, the piece table, per-segment first / count, state in /
+    // out, {records, payload bytes, pieces}; state_in goes up as hvws_utf8's does
+    dbuf mg_scan, mg_off, mg_tiles, mg_msgs, mg_first, mg_count, mg_in, mg_out, mg_meta;
+    hbuf h_mg_in;
+    hipEvent_t mg_up_ev = nullptr;
+    bool mg_up_pending = false;
+    bool have_msg = false;
+    uint32_t mg_nseg = 0;
     // small-batch path (k_small): upload packet, record slots, pinned results
     hbuf h_small_in, h_small_out;
     hbuf h_small_done;             // per-segment completion words k_small writes last
@@ -2267,7 +2276,8 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         for (dbuf* b : {&c->segs, &c->carry_in, &c->stage, &c->xor_stage, &c->synth_sizes, &c->synth_tiles, &c->synth_bad,
                         &c->tx_size, &c->tx_off, &c->tx_scan, &c->tx_tiles, &c->tx_stat, &c->tx_span, &c->d_small_in,
                         &c->d_small_slots, &c->u8_words, &c->u8_flags, &c->u8_tiles, &c->u8_meta, &c->u8_in, &c->u8_out,
-                        &c->u8_bad})
+                        &c->u8_bad, &c->mg_scan, &c->mg_off, &c->mg_tiles, &c->mg_msgs, &c->mg_first, &c->mg_count,
+                        &c->mg_in, &c->mg_out, &c->mg_meta})
             b->release();
         c->chk.release();
     }
@@ -2280,6 +2290,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->h_small_out.release();
         c->h_feed.release();
         c->h_u8_in.release();
+        c->h_mg_in.release();
         c->h_segs.release();
         for (hbuf& b : c->h_up) b.release();
         c->h_total.release();
@@ -2292,6 +2303,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
             if (t.free_ev) hipEventDestroy(t.free_ev);
         if (c->sv_ev) hipEventDestroy(c->sv_ev);
         if (c->u8_up_ev) hipEventDestroy(c->u8_up_ev);
+        if (c->mg_up_ev) hipEventDestroy(c->mg_up_ev);
         for (hipEvent_t ev : c->pipe_ev)
             if (ev) hipEventDestroy(ev);
         for (auto& ev : c->ev)
@@ -2636,6 +2648,173 @@ int hvws_get_utf8(hvws_ctx* c, uint32_t* state_out, uint64_t* bad) {
 }
 
 uint64_t hvws_utf8_tile(void) { return U8_TILE; }
+
+static_assert(sizeof(dmsg) == sizeof(hvws_msg) && sizeof(dmsg) == 40, "dmsg mirrors hvws_msg");
+static_assert(sizeof(dmsg_state) == sizeof(hvws_msg_state) && sizeof(dmsg_state) == 16,
+              "dmsg_state mirrors hvws_msg_state");
+static_assert(M_END == HVWS_M_END && M_CONT == HVWS_M_CONT, "piece bits");
+
+// Message reassembly over the last scan's frame table (hvws_msg.hip): the
+// table pass, the tile index over the output, the gather -- all on the context
+// stream, behind the scan (and the unmask of a step), reading rx and the
+// current table set only.
+int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
+                  const hvws_msg_state* state_in) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_messages without a preceding hvws_scan");
+    if (!d_rx || d_rx != c->rx || rx_len != c->rx_len)
+        return set_err(HVWS_EINVAL, "hvws_messages buffer differs from the scanned one");
+    if (!d_out || ((uintptr_t)d_out & 15u) != 0)
+        return set_err(HVWS_EINVAL, "hvws_messages: d_out must be 16-byte aligned");
+    {
+        const uintptr_t o = (uintptr_t)d_out, r = (uintptr_t)d_rx;
+        if (o < r + rx_len && r < o + out_cap) return set_err(HVWS_EINVAL, "hvws_messages: d_out overlaps the batch");
+    }
+    const uint32_t nseg = c->nseg;
+    if (state_in)
+        for (uint32_t s = 0; s < nseg; ++s)
+            if ((state_in[s].open == 0 && state_in[s].pending != 0) || state_in[s].opcode > 15)
+                return set_err(HVWS_EINVAL, "hvws_messages: state_in is no state hvws_get_msg_state returns");
+    // a RUN step left no frame table: build it now (as hvws_unmask does)
+    if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
+    // c->nfr: the record count, or its bound while the count is on the device
+    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
+    const uint64_t bound = std::min(rx_len, out_cap);   // the payload cannot exceed the batch
+    const int geom = msg_variant(rx_len, cap);
+    const uint64_t tile = msg_gather_tile(geom);
+    uint64_t ntiles = (bound + tile - 1) / tile;
+    HIP_OR(c->mg_scan.ensure(msg_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(c->mg_off.ensure(cap * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
+    HIP_OR(c->mg_msgs.ensure((cap + 1) * sizeof(dmsg)), HVWS_ENOMEM);
+    HIP_OR(c->mg_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_in.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_out.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_meta.ensure(64), HVWS_ENOMEM);
+    c->have_msg = false;   // the tables are being rewritten
+    if (state_in && nseg) {
+        const uint64_t bytes = (uint64_t)nseg * sizeof(dmsg_state);
+        if (!c->mg_up_ev) HIP_OR(hipEventCreateWithFlags(&c->mg_up_ev, hipEventDisableTiming), HVWS_EHIP);
+        if (c->mg_up_pending) {   // the previous pass's copy out of the slot
+            HIP_OR(hipEventSynchronize(c->mg_up_ev), HVWS_EHIP);
+            c->mg_up_pending = false;
+        }
+        HIP_OR(c->h_mg_in.ensure(bytes), HVWS_ENOMEM);
+        memcpy(c->h_mg_in.p, state_in, bytes);
+        HIP_OR(hipMemcpyAsync(c->mg_in.p, c->h_mg_in.p, bytes, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->mg_up_ev, c->stream), HVWS_EHIP);
+        c->mg_up_pending = true;
+    }
+    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    HIP_OR(launch_msg_table(c->T().f_len.as<uint64_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(), cap,
+                            c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), nseg,
+                            state_in ? c->mg_in.as<dmsg_state>() : nullptr, c->mg_scan.p, c->mg_off.as<uint64_t>(),
+                            c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
+                            c->mg_out.as<dmsg_state>(), c->mg_meta.as<uint64_t>(), c->stream),
+           HVWS_EHIP);
+    // Pipelined steps: the scan two steps on writes this table set and must
+    // wait for this pass as it waits for the set's unmask.
+    auto free_event = [&]() -> int {
+        if (c->piped) {
+            HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
+            c->T().free_wait = c->T().free_ev;
+            c->T().free_pending = true;
+        }
+        return HVWS_OK;
+    };
+    bool fits = true;
+    if (out_cap < rx_len) {   // the one wait: does the payload fit?
+        uint64_t total = 0;
+        HIP_OR(hipMemcpyAsync(&total, c->mg_meta.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+        HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+        fits = total <= out_cap;
+        ntiles = (std::min(total, out_cap) + tile - 1) / tile;
+    }
+    if (fits) {
+        if (ntiles)
+            HIP_OR(launch_tile_index(c->mg_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), 0, c->mg_meta.as<uint64_t>(),
+                                     c->mg_tiles.as<uint32_t>(), ntiles, tile, c->stream),
+                   HVWS_EHIP);
+        HIP_OR(launch_msg_gather(geom, d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
+                                 c->T().f_keyrot.as<uint32_t>(), c->mg_off.as<uint64_t>(), c->mg_tiles.as<uint32_t>(),
+                                 ntiles, c->mg_meta.as<uint64_t>(), masked, d_out, out_cap, c->stream),
+               HVWS_EHIP);
+    }
+    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
+    c->ev_build = true;
+    if ((rc = free_event()) != HVWS_OK) return rc;
+    if (!fits) return set_err(HVWS_EINVAL, "hvws_messages: the payload does not fit out_cap");
+    c->have_msg = true;
+    c->mg_nseg = nseg;
+    return HVWS_OK;
+}
+
+namespace {
+// meta word i of the last hvws_messages (1: payload bytes, 2: pieces); waits
+int msg_meta(hvws_ctx* c, int i, uint64_t* v) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    HIP_OR(hipMemcpyAsync(v, c->mg_meta.as<uint64_t>() + i, 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+}  // namespace
+
+int64_t hvws_msg_count(hvws_ctx* c) {
+    uint64_t n = 0;
+    if (!c || msg_meta(c, 2, &n) != HVWS_OK) return -1;
+    return (int64_t)n;
+}
+
+int hvws_msg_bytes(hvws_ctx* c, uint64_t* total) {
+    if (!total) return set_err(HVWS_EINVAL, "null output");
+    return msg_meta(c, 1, total);
+}
+
+int hvws_get_messages(hvws_ctx* c, hvws_msg* out, uint64_t first, uint64_t n) {
+    uint64_t have = 0;
+    int rc = msg_meta(c, 2, &have);
+    if (rc) return rc;
+    if (first > have || n > have - first) return set_err(HVWS_EINVAL, "piece range out of bounds");
+    if (n == 0) return HVWS_OK;
+    if (!out) return set_err(HVWS_EINVAL, "null output");
+    HIP_OR(hipMemcpyAsync(out, c->mg_msgs.as<dmsg>() + first, n * sizeof(dmsg), hipMemcpyDeviceToHost, c->stream),
+           HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int hvws_get_segment_messages(hvws_ctx* c, uint64_t* first, uint64_t* count) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    const uint64_t nseg = c->mg_nseg;
+    if (first && nseg) HIP_OR(hipMemcpyAsync(first, c->mg_first.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (count && nseg) HIP_OR(hipMemcpyAsync(count, c->mg_count.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int hvws_get_msg_state(hvws_ctx* c, hvws_msg_state* out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    const uint64_t nseg = c->mg_nseg;
+    if (out && nseg)
+        HIP_OR(hipMemcpyAsync(out, c->mg_out.p, nseg * sizeof(dmsg_state), hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+const hvws_msg* hvws_messages_device(hvws_ctx* c) {
+    if (!c || !c->have_msg) return nullptr;
+    return c->mg_msgs.as<hvws_msg>();
+}
+
+uint64_t hvws_msg_tile(void) { return MSG_TILE; }
 
 int hvws_step_resident(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len, const hvws_segment* segs,
                        const websocket_parser* carry_in, uint32_t nseg) {

@@ -490,6 +490,39 @@ hipError_t launch_utf8(const uint8_t* rx, uint64_t rx_len, const uint64_t* pay_o
                        const uint32_t* tile_first, uint64_t ntiles, int masked, uint32_t* flags, uint32_t* words,
                        uint64_t* meta, const uint64_t* counts, const uint64_t* bases, uint32_t nseg,
                        const uint32_t* state_in, uint32_t* state_out, uint64_t* bad, hipStream_t st);
+// Message reassembly (hvws_msg.hip; include/hvws.h has the rule, the layout
+// and the carry).  dmsg_state / dmsg mirror hvws_msg_state / hvws_msg.
+struct dmsg_state {
+    uint64_t pending;
+    uint32_t opcode, open;
+};
+struct dmsg {
+    uint64_t off, len, total, rec;
+    uint32_t seg, info;
+};
+enum : uint32_t { M_END = 1u << 4, M_CONT = 1u << 5 };
+constexpr uint64_t MSG_TILE = 16384;   // output bytes of k_msg_gather's largest tile (every geometry's divides it)
+// k_msg_gather geometry for a batch of rx_len bytes in at most cap records
+// ($HVWS_EXPERIMENT msg, else by the mean bytes per record) and its tile
+int msg_variant(uint64_t rx_len, uint64_t cap);
+uint64_t msg_gather_tile(int g);
+uint64_t msg_scratch_bytes(uint64_t cap);
+// The table pass, reading the frame table only.  nfr_dev / cap as for
+// launch_utf8; scratch: msg_scratch_bytes(cap); out_off: cap words; msgs:
+// cap + 1 entries; state_in (device, nullptr: all fresh) -> state_out;
+// meta[0..2] = records, payload bytes, pieces.
+hipError_t launch_msg_table(const uint64_t* pay_len, const uint32_t* info, const uint64_t* nfr_dev, uint64_t cap,
+                            const uint64_t* counts, const uint64_t* bases, uint32_t nseg, const dmsg_state* state_in,
+                            void* scratch, uint64_t* out_off, dmsg* msgs, uint64_t* seg_first, uint64_t* seg_count,
+                            dmsg_state* state_out, uint64_t* meta, hipStream_t st);
+// The gather, geometry g: tile_first is launch_tile_index over (out_off,
+// pay_len, meta) at msg_gather_tile(g) with ntiles tiles (ntiles tiles hold
+// the payload bytes; tiles beyond them do nothing).  Writes
+// out[0 .. min(meta[1], out_cap)) only.
+hipError_t launch_msg_gather(int g, const uint8_t* rx, uint64_t rx_len, const uint64_t* pay_off, const uint64_t* pay_len,
+                             const uint32_t* keyrot, const uint64_t* out_off, const uint32_t* tile_first,
+                             uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
+                             hipStream_t st);
 // Predicted frames above which a uniform segment is verified grid-wide (k_verify).
 uint64_t spec_min();
 uint64_t set_spec_min(uint64_t v);   // 0 = default; returns the previous value

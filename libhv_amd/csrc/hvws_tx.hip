@@ -6,11 +6,9 @@
 // out of place from a payload buffer into the frame buffer.
 #include <stdlib.h>
 
-#include "hvws_internal.h"
+#include "hvws_dev.h"
 
 namespace hvws {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t tx_hdr_len(uint32_t flags, uint64_t n) {
     const uint32_t ext = n < 126 ? 0u : (n <= 0xFFFFu ? 2u : 8u);
@@ -27,55 +25,9 @@ __device__ __forceinline__ uint32_t tx_hdr_byte(uint32_t flags, uint64_t n, uint
     return (key >> (8 * (h - 2 - ext))) & 0xFFu;
 }
 
-// ---- device-wide exclusive scan of u64 (block sums, scan of sums, add) ----
-// 256-thread workgroups, 4 consecutive elements per thread (1024 per block).
-// Workgroups of 1024 threads waited 125-200 us each for a CU with 16 free
-// wave slots while a pipelined unmask held the device (the frame sieve's
-// scans, profiles/r2o_raw), against ~5 us alone.
-constexpr int SCAN_T = 256;
-constexpr int SCAN_I = 4;
-constexpr int SCAN_B = SCAN_T * SCAN_I;
-
-__global__ __launch_bounds__(SCAN_T) void k_scan_blocks(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
-                                                        uint64_t n, uint64_t* __restrict__ block_sums,
-                                                        uint64_t* __restrict__ total_if_one) {
-    __shared__ uint64_t s[SCAN_T];
-    const uint32_t t = threadIdx.x;
-    const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)t * SCAN_I;
-    uint64_t v[SCAN_I], sum = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_I; ++k) {
-        v[k] = i0 + k < n ? in[i0 + k] : 0;
-        sum += v[k];
-    }
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < SCAN_T; d <<= 1) {
-        const uint64_t a = t >= (unsigned)d ? s[t - d] : 0;
-        __syncthreads();
-        s[t] += a;
-        __syncthreads();
-    }
-    uint64_t run = s[t] - sum;   // exclusive within the block
-#pragma unroll
-    for (int k = 0; k < SCAN_I; ++k) {
-        if (i0 + k < n) out[i0 + k] = run;
-        run += v[k];
-    }
-    if (t == SCAN_T - 1) {
-        block_sums[blockIdx.x] = s[t];
-        if (total_if_one) *total_if_one = s[t];   // one block: its sum is the total
-    }
-}
-
-__global__ __launch_bounds__(SCAN_T) void k_add_block_base(uint64_t* __restrict__ out, uint64_t n,
-                                                           const uint64_t* __restrict__ block_base) {
-    const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)threadIdx.x * SCAN_I;
-    const uint64_t b = block_base[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SCAN_I; ++k)
-        if (i0 + k < n) out[i0 + k] += b;
-}
+// (The device-wide exclusive scan -- k_scan_blocks, k_add_block_base -- and the
+// realigning helpers ld16_any, funnel16 and put_bytes live in hvws_dev.h: the
+// message pass, hvws_msg.hip, uses them too.)
 
 // ------------------------------------------------------------- k_build
 //
@@ -89,66 +41,9 @@ __global__ __launch_bounds__(SCAN_T) void k_add_block_base(uint64_t* __restrict_
 // table within the tile's frame range, then 16 payload bytes or, at headers
 // and frame boundaries, byte by byte.
 
-// 16 payload bytes starting at arbitrary offset p of a buffer of plen bytes.
-__device__ __forceinline__ void ld16_any(const uint8_t* pay, uint64_t plen, uint64_t p, uint64_t& lo, uint64_t& hi) {
-    const uint64_t a = p & ~15ull;
-    const uint32_t s = (uint32_t)(p & 15u);
-    if (a + 32 <= plen) {
-        const u32x4 va = *reinterpret_cast<const u32x4*>(pay + a);
-        const u32x4 vb = *reinterpret_cast<const u32x4*>(pay + a + 16);
-        const uint64_t w0 = va.x | ((uint64_t)va.y << 32), w1 = va.z | ((uint64_t)va.w << 32);
-        const uint64_t w2 = vb.x | ((uint64_t)vb.y << 32), w3 = vb.z | ((uint64_t)vb.w << 32);
-        const uint64_t x0 = s < 8 ? w0 : w1, x1 = s < 8 ? w1 : w2, x2 = s < 8 ? w2 : w3;
-        const uint32_t sh = (s & 7u) * 8u;
-        lo = sh ? (x0 >> sh) | (x1 << (64u - sh)) : x0;
-        hi = sh ? (x1 >> sh) | (x2 << (64u - sh)) : x1;
-    } else {
-        lo = hi = 0;
-        for (int b = 0; b < 16; ++b) {
-            const uint64_t q = p + b;
-            const uint64_t v = q < plen ? pay[q] : 0;
-            if (b < 8) lo |= v << (8 * b);
-            else hi |= v << (8 * (b - 8));
-        }
-    }
-}
-
-// bytes s..s+15 of the 32-byte little-endian pair (a, b), s in [0, 16)
-__device__ __forceinline__ u32x4 funnel16(u32x4 a, u32x4 b, uint32_t s) {
-    const uint64_t w0 = a.x | ((uint64_t)a.y << 32), w1 = a.z | ((uint64_t)a.w << 32);
-    const uint64_t w2 = b.x | ((uint64_t)b.y << 32), w3 = b.z | ((uint64_t)b.w << 32);
-    const uint64_t x0 = s < 8 ? w0 : w1, x1 = s < 8 ? w1 : w2, x2 = s < 8 ? w2 : w3;
-    const uint32_t sh = (s & 7u) * 8u;
-    const uint64_t lo = sh ? (x0 >> sh) | (x1 << (64u - sh)) : x0;
-    const uint64_t hi = sh ? (x1 >> sh) | (x2 << (64u - sh)) : x1;
-    return u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-}
-
 constexpr uint32_t BUILD_MAXF = 128;   // frames per boundary tile staged in LDS
 
 __device__ __forceinline__ uint32_t tx_rotr(uint32_t x, uint32_t r) { return r ? (x >> r) | (x << (32u - r)) : x; }
-
-// OR bytes [0, b1 - b0) of the 16-byte little-endian value (vlo, vhi) into
-// bytes [b0, b1) of the chunk (olo, ohi); 0 <= b0 < b1 <= 16.
-__device__ __forceinline__ void put_bytes(uint64_t& olo, uint64_t& ohi, uint64_t vlo, uint64_t vhi, uint32_t b0,
-                                          uint32_t b1) {
-    const uint32_t n = b1 - b0;
-    if (n < 8) {
-        vlo &= ~0ull >> (64u - 8u * n);
-        vhi = 0;
-    } else if (n < 16) {
-        vhi = n == 8 ? 0 : vhi & (~0ull >> (64u - 8u * (n - 8u)));
-    }
-    if (b0 >= 8) {
-        vhi = vlo << (8u * (b0 - 8u));
-        vlo = 0;
-    } else if (b0) {
-        vhi = (vhi << (8u * b0)) | (vlo >> (64u - 8u * b0));
-        vlo <<= 8u * b0;
-    }
-    olo |= vlo;
-    ohi |= vhi;
-}
 
 // Frame header as a 16-byte little-endian value (bytes beyond its length 0);
 // layout of http/websocket_parser.c:215-246 (same bytes as tx_hdr_byte).
@@ -886,18 +781,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(C == 2 ? 7 : 
 
 hipError_t launch_exclusive_scan(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, uint64_t* total,
                                  hipStream_t st) {
-    if (n == 0) return hipMemsetAsync(total, 0, 8, st);
-    const uint64_t nb = (n + SCAN_B - 1) / SCAN_B;
-    uint64_t* sums = tmp;
-    uint64_t* base = tmp + nb;
-    hipLaunchKernelGGL(k_scan_blocks, dim3((uint32_t)nb), dim3(SCAN_T), 0, st, in, out, n, sums,
-                       nb == 1 ? total : (uint64_t*)nullptr);
-    if (nb > 1) {
-        hipError_t e = launch_exclusive_scan(sums, base, nb, tmp + 2 * nb, total, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_add_block_base, dim3((uint32_t)nb), dim3(SCAN_T), 0, st, out, n, base);
-    }
-    return hipGetLastError();
+    return launch_scan_of(scan_from_array<uint64_t>{in}, out, n, tmp, total, st);
 }
 
 // stat[1] += frames whose payload range leaves [0, plen) or that are masked
