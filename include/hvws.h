@@ -374,6 +374,9 @@ int hvws_rx_batch(hvws_ctx* ctx, uint8_t* h_rx, uint64_t len, const hvws_segment
  * connection closes (http/server/HttpHandler.cpp:757-763); on_frame_header
  * is not called for it.  A header split across reads keeps its partial
  * validation state in the padding byte after websocket_parser.mask_offset.
+ * A step under validation never takes the RUN path, even with
+ * hvws_set_run(ctx, 1); the records of a RUN step read after a later
+ * hvws_set_validation are those of the classes in force when it ran (none).
  * Returns the previous classes. */
 uint32_t hvws_set_validation(hvws_ctx* ctx, uint32_t classes);
 

@@ -214,6 +214,7 @@ struct hvws_ctx {
     uint32_t run_skip = 0;     // steps left before RUN is tried again after a failed hypothesis
     uint64_t run_seq = 0;      // the current RUN step's verdict number
     uint64_t run_seen = 0;     // the last verdict read (dspec_status::run_seq)
+    uint32_t run_vmask = 0;    // validation classes in force when the current RUN step ran (run_materialize)
     uint64_t last_mean = 0;    // bytes per record of the last exact (or SPEC) scan: RUN is for small frames
     // frame sieve (hvws_sieve.hip): one long mixed-size segment discovered in
     // parallel.  h_sv receives the device state + survivor and chain counts
@@ -941,6 +942,7 @@ int scan_run(scan_job& j) {
     HIP_OR(issue_pass(j, SCAN_RUN), HVWS_EHIP);
     c->run_seq = ++c->scan_seq;
     c->run_active = true;
+    c->run_vmask = c->vmask;
     c->nseg = j.nseg;   // issue_unmask reads it
     if (c->cs != c->stream) {   // pipelined: host-ordered, as SPEC (checked_attempt)
         HIP_OR(launch_publish_tiles(j.status_d, c->run_seq, c->cs), HVWS_EHIP);
@@ -1122,7 +1124,10 @@ int scan_device_carry(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, uint32_
 // The records of a RUN step, built when a reader asks for them: an exact scan
 // of the same batch (its headers never change; its segment and carry tables
 // are the device copies the RUN scan wrote) on the context stream, behind
-// the unmask and its repair.  The scan path stays RUN.
+// the unmask and its repair.  The scan path stays RUN, and the records are
+// those of the validation classes in force when the step ran (none: a step
+// under validation never takes the RUN path), whatever hvws_set_validation
+// has been told since.
 int run_materialize(hvws_ctx* c) {
     if (!c->run_active) return HVWS_OK;
     c->run_active = false;
@@ -1130,11 +1135,14 @@ int run_materialize(hvws_ctx* c) {
     hipStream_t cs = c->cs;
     c->cs = c->stream;
     const bool call = c->run_call, t_on = c->t_on;
+    const uint32_t vmask = c->vmask;
     c->run_call = false;
     c->t_on = false;   // the RUN step's events stay in its slot (hvws_last_times / hvws_step_times)
+    c->vmask = c->run_vmask;
     c->materializing = true;
     const int rc = scan_device_carry(c, c->rx, c->rx_len, c->nseg);
     c->materializing = false;
+    c->vmask = vmask;
     c->t_on = t_on;
     c->run_call = call;
     c->cs = cs;
