@@ -26,6 +26,15 @@
  *                (http/WebSocketParser.cpp:8-75) for a whole batch: the
  *                payload bytes with the headers squeezed out, unmasked on the
  *                way, and the table of the messages they form -- on the device.
+ *   hvws_send_messages  WebSocketChannel::send (http/WebSocketChannel.cpp:5-48)
+ *                for a batch of messages: one frame each, or fragmented into
+ *                OPCODE, CONTINUE ..., CONTINUE + FIN, from a message table
+ *                that may exist only on the device.
+ *   hvws_replies  the server's onMessage dispatch (http/server/HttpHandler.cpp:
+ *                174-200) over the pieces of hvws_messages: a PONG for every
+ *                PING, a CLOSE for the first CLOSE and nothing after it,
+ *                optionally an echo of data messages -- as a message table
+ *                hvws_send_messages sends without a host read in between.
  *   hvws_wsp_*   C handle over the WebSocketParser class
  *                (http/WebSocketParser.h:19-31) for FFI callers.
  *
@@ -333,8 +342,9 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
  * kernel, or of the last hvws_build_frames' device work after its size check
  * (tile index, source spans, k_build), or of the last hvws_utf8 (its tile
  * index and all three kernels), or of the last hvws_messages (table pass,
- * tile index and gather) -- whichever was called last; the default
- * build geometry's name. */
+ * tile index and gather), or of the last hvws_send_messages' device work after
+ * its wait (expansion, tile index, spans, k_build) -- whichever was called
+ * last; the default build geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
 const char* hvws_build_kernel_name(void);
 /* The k_build geometry the last hvws_build_frames on ctx ran: one-wave
@@ -554,6 +564,120 @@ const hvws_msg* hvws_messages_device(hvws_ctx* ctx);
  * (tests place record boundaries around its multiples).  Results never depend
  * on the geometry. */
 uint64_t hvws_msg_tile(void);
+
+/* ---- batched send, device resident ---------------------------------------- */
+/* WebSocketChannel::send (http/WebSocketChannel.cpp:5-48) for n messages at
+ * once.  Message i is the bytes [off, off + len) of d_payload and goes out
+ * exactly as the reference's send(buf, len, fragment, opcode) builds it, with
+ * F = fragment (0 = 65535, the reference's default) and L = len:
+ *   - L <= F (L = 0 included): one frame with the message's opcode, its FIN bit
+ *     taken from flags (send()'s `fin`);
+ *   - otherwise ceil(L / F) frames: the first with the opcode and FIN clear,
+ *     then CONTINUE frames of F bytes, then a last CONTINUE frame of
+ *     L - (frames - 1) * F bytes (1 .. F) with FIN set.
+ * Two reference quirks are reproduced: a fragmented message always ends with
+ * FIN (the 4-argument send drops its `fin` argument when it fragments), and
+ * control opcodes are fragmented like any other (send(msg, WS_OPCODE_PONG) with
+ * a long message does that).
+ *
+ * Each frame is byte-identical to websocket_build_frame for its flags, length
+ * and key.  masked == 0: server frames, no key; masked == 1: every frame has
+ * WS_HAS_MASK, and where the reference draws rand() per frame, fragment j of a
+ * message with key k uses hvws_frag_key(k, j).  Frames lie back to back in
+ * d_out, messages in table order; messages may overlap or coincide in
+ * d_payload (a broadcast).
+ *
+ * d_n (optional): a device word holding the message count; the effective count
+ * is min(*d_n, n), read on the device (hvws_reply_count_device: the reply table
+ * is sent without a wait in between).  d_msg_off (optional): effective count
+ * + 1 words, the output offset of each message's first frame and the total in
+ * the last.  *out_len receives the total bytes, *out_frames the frame count.
+ *
+ * Waits once, as hvws_build_frames does: after the message pass the host reads
+ * {frames, bytes, bad messages}.  A message outside [0, payload_len), a flag
+ * bit outside 0x1F, more than 2^32 - 2 frames, or a total above out_cap
+ * (*out_len is still set then) is HVWS_EINVAL with nothing written to d_out; a
+ * bad message adds nothing to the sums, and the sums saturate instead of
+ * wrapping.  Everything after the wait is asynchronous on the ctx stream.
+ * d_out must be 16-byte aligned and must not overlap d_payload.
+ * hvws_last_kernel_ms reports the device work after the wait (expansion into
+ * frames, tile index, spans, build) when this was the last call;
+ * hvws_last_build_kernel / hvws_last_build_uniform report its k_build.
+ * Results never depend on the geometry or on whether a uniform layout (every
+ * message one frame of one length, payloads at a constant step) was found. */
+typedef struct hvws_tx_msg {   /* 24 B */
+    uint64_t off, len;         /* the message's bytes in d_payload */
+    uint32_t flags;            /* bits 0-3 opcode, WS_FIN (0x10) = send()'s `fin`; any other bit: HVWS_EINVAL */
+    uint32_t key;              /* masking key of the message, mask[0] in bits 0-7; used only when masked */
+} hvws_tx_msg;
+/* The key of fragment j of a message with key k (j = 0: k itself). */
+static inline uint32_t hvws_frag_key(uint32_t k, uint32_t j) {
+    uint32_t x = k + j * 0x9E3779B9u;
+    if (j == 0) return k;
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+int hvws_send_messages(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uint8_t* d_payload, uint64_t payload_len,
+                       const hvws_tx_msg* d_msgs, uint64_t n, const uint64_t* d_n, uint64_t fragment, int masked,
+                       uint64_t* d_msg_off, uint64_t* out_len, uint64_t* out_frames);
+
+/* ---- server replies, device resident ------------------------------------- */
+/* What the server's onMessage does with each message of the last
+ * hvws_messages (http/server/HttpHandler.cpp:174-200), as a table of messages
+ * to send.  Over that call's pieces in table order; only pieces with
+ * HVWS_M_END count, and op is the piece's opcode (info & 0xF: what onMessage
+ * reports, quirks Q5 and Q6 of SURVEY.md Appendix A included):
+ *   - op 9 with HVWS_R_PONG in the policy: a reply with opcode 10;
+ *   - op 8 with HVWS_R_CLOSE: a reply with opcode 8;
+ *   - op 1 or 2 with HVWS_R_ECHO: a reply with the same opcode;
+ *   - anything else: none.
+ * Every reply has FIN set and carries the piece's bytes: off / len index the
+ * d_out of that hvws_messages.
+ * Close is final: after a segment's first piece selected as a CLOSE no later
+ * piece of the segment produces a reply (Channel::close() sets CLOSED and
+ * write() then fails, evpp/Channel.h:154-156,189-197); a segment with
+ * closed_in[s] set produces none at all.  Both leave HVWS_RF_CLOSED in the
+ * segment's flags: the caller carries it beside its other per-connection
+ * state and closes the socket.
+ * Deferred: a selected piece whose total != len completes a message begun in
+ * an earlier batch; its bytes are not all in this d_out, so it produces no
+ * reply here and its segment gets HVWS_RF_DEFERRED.  Only a segment's first
+ * piece can be in this position: the host builds that one reply from its own
+ * copy and sends it before the segment's device replies.  A deferred CLOSE
+ * still closes the segment for the pieces after it.
+ * Replies are dense, ordered by segment and then stream order, so each
+ * segment's reply frames are contiguous in the send's output: from
+ * d_msg_off[first[s]] to d_msg_off[first[s] + count[s]].
+ *
+ * hvws_replies runs after hvws_messages (none before it: HVWS_EINVAL), is
+ * asynchronous on the ctx stream and does not wait.  closed_in: host, nseg
+ * bytes, NULL = none.  Its results are valid until the next hvws_replies or
+ * hvws_messages on ctx.  hvws_replies_device / hvws_reply_count_device: the
+ * table and its count in device memory (d_msgs and d_n of
+ * hvws_send_messages); hvws_reply_capacity: the entries the table holds (its
+ * n).  hvws_reply_count, hvws_get_replies (replies first .. first + n - 1 and
+ * the piece each answers; either may be NULL), hvws_get_segment_replies (per
+ * segment, its first reply and reply count) and hvws_get_reply_flags (per
+ * segment, HVWS_RF_*) wait. */
+#define HVWS_R_PONG   1u  /* PING  -> PONG with the ping's message        (HttpHandler.cpp:181-185) */
+#define HVWS_R_CLOSE  2u  /* CLOSE -> CLOSE with the same message; the
+                             connection sends nothing after it             (HttpHandler.cpp:177-180) */
+#define HVWS_R_ECHO   4u  /* TEXT / BINARY -> same opcode and bytes (an echo service's onmessage) */
+#define HVWS_R_SERVER (HVWS_R_PONG | HVWS_R_CLOSE)
+#define HVWS_RF_CLOSED   1u
+#define HVWS_RF_DEFERRED 2u
+int hvws_replies(hvws_ctx* ctx, uint32_t policy, const uint8_t* closed_in);
+const hvws_tx_msg* hvws_replies_device(hvws_ctx* ctx);
+const uint64_t* hvws_reply_count_device(hvws_ctx* ctx);
+uint64_t hvws_reply_capacity(hvws_ctx* ctx);
+int64_t hvws_reply_count(hvws_ctx* ctx);
+int hvws_get_replies(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* piece, uint64_t first, uint64_t n);
+int hvws_get_segment_replies(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+int hvws_get_reply_flags(hvws_ctx* ctx, uint8_t* out);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -78,6 +78,12 @@ MSG_DTYPE = np.dtype(
 MSG_STATE_DTYPE = np.dtype([("pending", "<u8"), ("opcode", "<u4"), ("open", "<u4")])
 assert MSG_DTYPE.itemsize == 40 and MSG_STATE_DTYPE.itemsize == 16
 MSG_END, MSG_CONT = 1 << 4, 1 << 5
+# hvws_tx_msg, HVWS_R_* and HVWS_RF_* (include/hvws.h)
+TX_MSG_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8"), ("flags", "<u4"), ("key", "<u4")])
+assert TX_MSG_DTYPE.itemsize == 24
+R_PONG, R_CLOSE, R_ECHO = 1, 2, 4
+R_SERVER = R_PONG | R_CLOSE
+RF_CLOSED, RF_DEFERRED = 1, 2
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -173,6 +179,22 @@ _SIGS = {
     "hvws_get_msg_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_messages_device": (ctypes.c_void_p, [ctypes.c_void_p]),
     "hvws_msg_tile": (ctypes.c_uint64, []),
+    "hvws_send_messages": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "hvws_replies": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "hvws_replies_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_reply_count_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_reply_capacity": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "hvws_reply_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_replies": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
+    ),
+    "hvws_get_segment_replies": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_get_reply_flags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -556,6 +578,60 @@ class Engine:
         n = ctypes.c_uint64(0)
         _check(lib().hvws_msg_bytes(self.ctx, ctypes.byref(n)), "hvws_msg_bytes")
         return int(n.value)
+
+    def send_messages(self, out: DeviceBuffer, out_cap: int, payload, payload_len: int, msgs, n: int,
+                      d_n=None, fragment: int = 0, masked: bool = False,
+                      msg_off: Optional[DeviceBuffer] = None) -> Tuple[int, int]:
+        """hvws_send_messages: WebSocketChannel::send for the first min(*d_n, n)
+        entries of the device table `msgs` (TX_MSG_DTYPE) over `payload`.  payload,
+        msgs and d_n are DeviceBuffers or device addresses (replies_device()).
+        Returns (bytes, frames); the build runs asynchronously on the ctx stream."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        nbytes, nfr = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = lib().hvws_send_messages(self.ctx, dev(out), out_cap, dev(payload), payload_len, dev(msgs), n, dev(d_n),
+                                      fragment, int(bool(masked)), dev(msg_off), ctypes.byref(nbytes),
+                                      ctypes.byref(nfr))
+        self.last_send_len = int(nbytes.value)   # set even when the call fails for out_cap
+        _check(rc, "hvws_send_messages")
+        return int(nbytes.value), int(nfr.value)
+
+    def replies(self, policy: int, closed_in=None) -> None:
+        """hvws_replies over the last messages() call: the server's onMessage
+        dispatch as a reply table on the device.  closed_in: one byte per segment."""
+        ci = None
+        if closed_in is not None:
+            ci = np.ascontiguousarray(closed_in, dtype=np.uint8)
+        _check(lib().hvws_replies(self.ctx, policy, ci.ctypes.data if ci is not None else None), "hvws_replies")
+
+    def replies_device(self) -> Tuple[int, int, int]:
+        """(table address, count word address, table capacity): msgs, d_n and n of
+        send_messages for the last replies() call; no wait."""
+        L = lib()
+        return L.hvws_replies_device(self.ctx), L.hvws_reply_count_device(self.ctx), L.hvws_reply_capacity(self.ctx)
+
+    def reply_table(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(replies [TX_MSG_DTYPE], the piece each answers) of the last replies() call."""
+        n = lib().hvws_reply_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_reply_count")
+        out = np.zeros(n, dtype=TX_MSG_DTYPE)
+        piece = np.zeros(n, dtype=np.uint64)
+        _check(lib().hvws_get_replies(self.ctx, out.ctypes.data, piece.ctypes.data, 0, n), "hvws_get_replies")
+        return out, piece
+
+    def segment_replies(self, nseg: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(first reply, reply count) per segment of the last replies() call."""
+        first = np.zeros(max(nseg, 1), np.uint64)
+        cnt = np.zeros(max(nseg, 1), np.uint64)
+        _check(lib().hvws_get_segment_replies(self.ctx, first.ctypes.data, cnt.ctypes.data),
+               "hvws_get_segment_replies")
+        return first[:nseg], cnt[:nseg]
+
+    def reply_flags(self, nseg: int) -> np.ndarray:
+        """RF_* per segment of the last replies() call."""
+        out = np.zeros(max(nseg, 1), np.uint8)
+        _check(lib().hvws_get_reply_flags(self.ctx, out.ctypes.data), "hvws_get_reply_flags")
+        return out[:nseg]
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

@@ -258,6 +258,22 @@ struct hvws_ctx {
     bool mg_up_pending = false;
     bool have_msg = false;
     uint32_t mg_nseg = 0;
+    uint64_t mg_cap = 0;   // the piece bound of the last hvws_messages (its record capacity)
+    // hvws_send_messages: the message scan's scratch, each message's first
+    // frame, {frames, bytes, bad, count, uniform layout}, and the per-frame rows
+    // k_build reads (out_off and size in tx_off / tx_size)
+    dbuf sd_scan, sd_first, sd_meta, sd_poff, sd_len, sd_flags, sd_mask;
+    // hvws_replies: the scan's scratch (word rp_cap of it: the reply count),
+    // each segment's closing limit, the reply table and the piece each reply
+    // answers, per-segment first / count / flags; closed_in goes up as
+    // hvws_messages' state_in does
+    dbuf rp_scan, rp_limit, rp_msgs, rp_piece, rp_first, rp_count, rp_flags, rp_closed;
+    hbuf h_rp_in;
+    hipEvent_t rp_up_ev = nullptr;
+    bool rp_up_pending = false;
+    bool have_rep = false;
+    uint32_t rp_nseg = 0;
+    uint64_t rp_cap = 0;
     // small-batch path (k_small): upload packet, record slots, pinned results
     hbuf h_small_in, h_small_out;
     hbuf h_small_done;             // per-segment completion words k_small writes last
@@ -2285,7 +2301,9 @@ void hvws_ctx_destroy(hvws_ctx* c) {
                         &c->tx_size, &c->tx_off, &c->tx_scan, &c->tx_tiles, &c->tx_stat, &c->tx_span, &c->d_small_in,
                         &c->d_small_slots, &c->u8_words, &c->u8_flags, &c->u8_tiles, &c->u8_meta, &c->u8_in, &c->u8_out,
                         &c->u8_bad, &c->mg_scan, &c->mg_off, &c->mg_tiles, &c->mg_msgs, &c->mg_first, &c->mg_count,
-                        &c->mg_in, &c->mg_out, &c->mg_meta})
+                        &c->mg_in, &c->mg_out, &c->mg_meta, &c->sd_scan, &c->sd_first, &c->sd_meta, &c->sd_poff,
+                        &c->sd_len, &c->sd_flags, &c->sd_mask, &c->rp_scan, &c->rp_limit, &c->rp_msgs, &c->rp_piece,
+                        &c->rp_first, &c->rp_count, &c->rp_flags, &c->rp_closed})
             b->release();
         c->chk.release();
     }
@@ -2299,6 +2317,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->h_feed.release();
         c->h_u8_in.release();
         c->h_mg_in.release();
+        c->h_rp_in.release();
         c->h_segs.release();
         for (hbuf& b : c->h_up) b.release();
         c->h_total.release();
@@ -2312,6 +2331,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         if (c->sv_ev) hipEventDestroy(c->sv_ev);
         if (c->u8_up_ev) hipEventDestroy(c->u8_up_ev);
         if (c->mg_up_ev) hipEventDestroy(c->mg_up_ev);
+        if (c->rp_up_ev) hipEventDestroy(c->rp_up_ev);
         for (hipEvent_t ev : c->pipe_ev)
             if (ev) hipEventDestroy(ev);
         for (auto& ev : c->ev)
@@ -2702,6 +2722,7 @@ int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     HIP_OR(c->mg_out.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_meta.ensure(64), HVWS_ENOMEM);
     c->have_msg = false;   // the tables are being rewritten
+    c->have_rep = false;   // ... which a reply table indexes
     if (state_in && nseg) {
         const uint64_t bytes = (uint64_t)nseg * sizeof(dmsg_state);
         if (!c->mg_up_ev) HIP_OR(hipEventCreateWithFlags(&c->mg_up_ev, hipEventDisableTiming), HVWS_EHIP);
@@ -2756,6 +2777,7 @@ int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     if (!fits) return set_err(HVWS_EINVAL, "hvws_messages: the payload does not fit out_cap");
     c->have_msg = true;
     c->mg_nseg = nseg;
+    c->mg_cap = cap;
     return HVWS_OK;
 }
 
@@ -3186,6 +3208,13 @@ int hvws_digest(hvws_ctx* c, const uint8_t* d_buf, uint64_t len, uint64_t* out) 
 }
 
 // --------------------------------------------------------------- transmit
+namespace {
+int tx_build_checked(hvws_ctx* c, uint8_t* d_out, uint64_t total, const uint8_t* d_payload, uint64_t payload_len,
+                     const uint64_t* d_pay_off, const uint64_t* d_len, const uint8_t* d_flags, const uint32_t* d_mask,
+                     const uint64_t* off, const uint64_t* size, uint64_t n, const uint64_t* uh,
+                     const std::function<hipError_t()>* pre);
+}  // namespace
+
 int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8_t* d_payload, uint64_t payload_len,
                       const uint64_t* d_pay_off, const uint64_t* d_len, const uint8_t* d_flags, const uint32_t* d_mask,
                       uint64_t n, uint64_t* d_out_off, uint64_t* out_len) {
@@ -3225,6 +3254,21 @@ int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8
     if (total > out_cap)
         return set_err(HVWS_EINVAL, "build_frames: output needs %llu bytes, capacity %llu", (unsigned long long)total,
                        (unsigned long long)out_cap);
+    return tx_build_checked(c, d_out, total, d_payload, payload_len, d_pay_off, d_len, d_flags, d_mask, off,
+                            c->tx_size.as<uint64_t>(), n, h + 2, nullptr);
+}
+
+namespace {
+// The half of hvws_build_frames after its wait, shared with
+// hvws_send_messages: n frames (rows d_pay_off .. size, total output bytes)
+// whose tables the device has checked.  uh = {frames breaking the uniform
+// layout, pay_off[0], its step, len[0]} (k_tx_check's stat[2..5]).  pre (may
+// be null): device work queued inside the timed region ahead of the tile
+// index (the send's expansion writes the rows there).
+int tx_build_checked(hvws_ctx* c, uint8_t* d_out, uint64_t total, const uint8_t* d_payload, uint64_t payload_len,
+                     const uint64_t* d_pay_off, const uint64_t* d_len, const uint8_t* d_flags, const uint32_t* d_mask,
+                     const uint64_t* off, const uint64_t* size, uint64_t n, const uint64_t* uh,
+                     const std::function<hipError_t()>* pre) {
     // the geometry by the batch's mean frame size (tx_variant); every layout
     // takes k_build (round 4: it reached or beat the same-offset kernel
     // k_build_id, which is gone, profiles/r4v_raw)
@@ -3244,8 +3288,8 @@ int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8
     // (small frames only, the lean form: at 64 KiB frames the index is ~0.1 %
     // of the call and the position-derived form measured slower at the rx
     // layout, 21.3 against 20.2 ms at c3, profiles/r5b_raw)
-    const bool uniform = uni_ok && v == 5 && h[2] == 0 && total % n == 0 && (n == 1 || h[4] >= h[5]);
-    const uint64_t uni[4] = {uniform ? total / n : 0, uniform ? total / n - h[5] : 0, h[3], h[4]};
+    const bool uniform = uni_ok && v == 5 && uh[0] == 0 && total % n == 0 && (n == 1 || uh[2] >= uh[3]);
+    const uint64_t uni[4] = {uniform ? total / n : 0, uniform ? total / n - uh[3] : 0, uh[1], uh[2]};
     c->tx_uniform = uniform;
     if (!uniform) {
         HIP_OR(c->tx_tiles.ensure((ntiles + 2) * 4), HVWS_ENOMEM);
@@ -3254,15 +3298,203 @@ int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8
     // the timed device work (hvws_last_kernel_ms): tile index, spans, build
     HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
     uint64_t* span = spans_ok && !uniform ? c->tx_span.as<uint64_t>() : nullptr;
+    if (pre) HIP_OR((*pre)(), HVWS_EHIP);
     if (!uniform)
-        HIP_OR(launch_tx_index(off, c->tx_size.as<uint64_t>(), d_pay_off, d_len, d_flags, n, ntiles, tile,
-                               c->tx_tiles.as<uint32_t>(), span, c->stream),
+        HIP_OR(launch_tx_index(off, size, d_pay_off, d_len, d_flags, n, ntiles, tile, c->tx_tiles.as<uint32_t>(), span,
+                               c->stream),
                HVWS_EHIP);
-    HIP_OR(launch_build(d_out, total, d_payload, payload_len, d_pay_off, d_len, d_flags, d_mask, off,
-                        c->tx_size.as<uint64_t>(), c->tx_tiles.as<uint32_t>(), span, n, v, c->stream, uni),
+    HIP_OR(launch_build(d_out, total, d_payload, payload_len, d_pay_off, d_len, d_flags, d_mask, off, size,
+                        c->tx_tiles.as<uint32_t>(), span, n, v, c->stream, uni),
            HVWS_EHIP);
     HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
     c->ev_build = true;
+    return HVWS_OK;
+}
+}  // namespace
+
+static_assert(sizeof(dtxmsg) == sizeof(hvws_tx_msg) && sizeof(dtxmsg) == 24, "dtxmsg mirrors hvws_tx_msg");
+static_assert(R_PONG == HVWS_R_PONG && R_CLOSE == HVWS_R_CLOSE && R_ECHO == HVWS_R_ECHO &&
+                  RF_CLOSED == HVWS_RF_CLOSED && RF_DEFERRED == HVWS_RF_DEFERRED,
+              "reply policy and flag bits");
+
+// WebSocketChannel::send for a batch (hvws_send.hip): the message pass, one
+// wait for {frames, bytes, bad}, then the expansion into per-frame rows and
+// hvws_build_frames' own index and k_build.
+int hvws_send_messages(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8_t* d_payload, uint64_t payload_len,
+                       const hvws_tx_msg* d_msgs, uint64_t n, const uint64_t* d_n, uint64_t fragment, int masked,
+                       uint64_t* d_msg_off, uint64_t* out_len, uint64_t* out_frames) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_len) *out_len = 0;
+    if (out_frames) *out_frames = 0;
+    if (n == 0) {
+        if (d_msg_off) HIP_OR(hipMemsetAsync(d_msg_off, 0, 8, c->stream), HVWS_EHIP);
+        return HVWS_OK;
+    }
+    if (!d_out || !d_msgs || (!d_payload && payload_len)) return set_err(HVWS_EINVAL, "send_messages: null table");
+    if (((uintptr_t)d_out & 15u) != 0) return set_err(HVWS_EINVAL, "send_messages: d_out must be 16-byte aligned");
+    {
+        const uintptr_t o = (uintptr_t)d_out, p = (uintptr_t)d_payload;
+        if (o < p + payload_len && p < o + out_cap)
+            return set_err(HVWS_EINVAL, "send_messages: d_out overlaps the payload buffer");
+    }
+    // every message has a frame
+    if (n >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "send_messages: %llu messages (max 2^32-2)", (unsigned long long)n);
+    const uint64_t F = fragment ? fragment : 0xFFFFu;   // WebSocketChannel.cpp:6
+    const dtxmsg* msgs = reinterpret_cast<const dtxmsg*>(d_msgs);
+    HIP_OR(c->sd_scan.ensure(send_scratch_bytes(n)), HVWS_ENOMEM);
+    HIP_OR(c->sd_first.ensure(n * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->sd_meta.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->h_tx.ensure(64), HVWS_ENOMEM);
+    uint64_t* meta = c->sd_meta.as<uint64_t>();
+    HIP_OR(hipMemsetAsync(meta, 0, 64, c->stream), HVWS_EHIP);
+    HIP_OR(launch_send_table(msgs, n, d_n, payload_len, F, masked, c->sd_scan.p, c->sd_first.as<uint64_t>(), d_msg_off,
+                             meta, c->stream),
+           HVWS_EHIP);
+    // [0] frames, [1] bytes, [2] bad messages, [3] effective count, [4] messages
+    // breaking the uniform layout, [5..7] off[0], its step, len[0]
+    uint64_t* h = c->h_tx.as<uint64_t>();
+    HIP_OR(hipMemcpyAsync(h, meta, 64, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    if (h[2])
+        return set_err(HVWS_EINVAL, "send_messages: %llu messages lie outside the payload buffer or have a flag bit "
+                       "outside 0x1F", (unsigned long long)h[2]);
+    const uint64_t nfr = h[0], total = h[1];
+    if (out_len) *out_len = total;
+    if (nfr > 0xFFFFFFFEull)
+        return set_err(HVWS_EINVAL, "send_messages: %llu frames (max 2^32-2)", (unsigned long long)nfr);
+    if (total > out_cap)
+        return set_err(HVWS_EINVAL, "send_messages: output needs %llu bytes, capacity %llu", (unsigned long long)total,
+                       (unsigned long long)out_cap);
+    if (out_frames) *out_frames = nfr;
+    if (nfr == 0) {   // *d_n was 0: nothing to build; the timed region is empty
+        HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
+        c->ev_build = true;
+        return HVWS_OK;
+    }
+    HIP_OR(c->sd_poff.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd_len.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd_flags.ensure(nfr + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd_mask.ensure(nfr * 4 + 8), HVWS_ENOMEM);
+    HIP_OR(c->tx_off.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->tx_size.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    const std::function<hipError_t()> expand = [&]() {
+        return launch_send_expand(msgs, c->sd_scan.p, c->sd_first.as<uint64_t>(), meta, nfr, F, masked,
+                                  c->sd_poff.as<uint64_t>(), c->sd_len.as<uint64_t>(), c->sd_flags.as<uint8_t>(),
+                                  c->sd_mask.as<uint32_t>(), c->tx_off.as<uint64_t>(), c->tx_size.as<uint64_t>(),
+                                  c->stream);
+    };
+    // the frames form a uniform layout when the messages do, one frame each
+    const uint64_t uh[4] = {h[4] + (nfr != h[3] ? 1u : 0u), h[5], h[6], h[7]};
+    return tx_build_checked(c, d_out, total, d_payload, payload_len, c->sd_poff.as<uint64_t>(),
+                            c->sd_len.as<uint64_t>(), c->sd_flags.as<uint8_t>(), c->sd_mask.as<uint32_t>(),
+                            c->tx_off.as<uint64_t>(), c->tx_size.as<uint64_t>(), nfr, uh, &expand);
+}
+
+// The server's onMessage dispatch over the last hvws_messages' pieces
+// (hvws_send.hip): no wait.
+int hvws_replies(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg) return set_err(HVWS_EINVAL, "hvws_replies without a preceding hvws_messages");
+    if (policy & ~(uint32_t)(HVWS_R_PONG | HVWS_R_CLOSE | HVWS_R_ECHO))
+        return set_err(HVWS_EINVAL, "hvws_replies: unknown policy bits");
+    const uint32_t nseg = c->mg_nseg;
+    const uint64_t cap = c->mg_cap;
+    HIP_OR(c->rp_scan.ensure(rep_scratch_words(cap) * 8), HVWS_ENOMEM);
+    HIP_OR(c->rp_limit.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp_msgs.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(c->rp_piece.ensure((cap + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(c->rp_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp_flags.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp_closed.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
+    c->have_rep = false;   // the tables are being rewritten
+    if (closed_in && nseg) {
+        if (!c->rp_up_ev) HIP_OR(hipEventCreateWithFlags(&c->rp_up_ev, hipEventDisableTiming), HVWS_EHIP);
+        if (c->rp_up_pending) {   // the previous call's copy out of the slot
+            HIP_OR(hipEventSynchronize(c->rp_up_ev), HVWS_EHIP);
+            c->rp_up_pending = false;
+        }
+        HIP_OR(c->h_rp_in.ensure(nseg), HVWS_ENOMEM);
+        memcpy(c->h_rp_in.p, closed_in, nseg);
+        HIP_OR(hipMemcpyAsync(c->rp_closed.p, c->h_rp_in.p, nseg, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->rp_up_ev, c->stream), HVWS_EHIP);
+        c->rp_up_pending = true;
+    }
+    HIP_OR(launch_replies(c->mg_msgs.as<dmsg>(), c->mg_meta.as<uint64_t>(), cap, c->mg_first.as<uint64_t>(),
+                          c->mg_count.as<uint64_t>(), nseg, policy, closed_in ? c->rp_closed.as<uint8_t>() : nullptr,
+                          c->rp_limit.as<uint64_t>(), c->rp_scan.as<uint64_t>(), c->rp_msgs.as<dtxmsg>(),
+                          c->rp_piece.as<uint64_t>(), c->rp_first.as<uint64_t>(), c->rp_count.as<uint64_t>(),
+                          c->rp_flags.as<uint8_t>(), c->stream),
+           HVWS_EHIP);
+    c->have_rep = true;
+    c->rp_nseg = nseg;
+    c->rp_cap = cap;
+    return HVWS_OK;
+}
+
+const hvws_tx_msg* hvws_replies_device(hvws_ctx* c) {
+    if (!c || !c->have_rep) return nullptr;
+    return c->rp_msgs.as<hvws_tx_msg>();
+}
+
+const uint64_t* hvws_reply_count_device(hvws_ctx* c) {
+    if (!c || !c->have_rep) return nullptr;
+    return c->rp_scan.as<uint64_t>() + c->rp_cap;
+}
+
+uint64_t hvws_reply_capacity(hvws_ctx* c) { return c && c->have_rep ? c->rp_cap : 0; }
+
+int64_t hvws_reply_count(hvws_ctx* c) {
+    if (check_ctx(c)) return -1;
+    if (!c->have_rep) {
+        set_err(HVWS_EINVAL, "no hvws_replies call yet");
+        return -1;
+    }
+    uint64_t n = 0;
+    if (hipMemcpyAsync(&n, c->rp_scan.as<uint64_t>() + c->rp_cap, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_err(HVWS_EHIP, "hvws_reply_count: reading the count failed");
+        return -1;
+    }
+    return (int64_t)n;
+}
+
+int hvws_get_replies(hvws_ctx* c, hvws_tx_msg* out, uint64_t* piece, uint64_t first, uint64_t n) {
+    const int64_t have = hvws_reply_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "reply range out of bounds");
+    if (n == 0) return HVWS_OK;
+    if (out)
+        HIP_OR(hipMemcpyAsync(out, c->rp_msgs.as<dtxmsg>() + first, n * sizeof(dtxmsg), hipMemcpyDeviceToHost, c->stream),
+               HVWS_EHIP);
+    if (piece)
+        HIP_OR(hipMemcpyAsync(piece, c->rp_piece.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost, c->stream),
+               HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int hvws_get_segment_replies(hvws_ctx* c, uint64_t* first, uint64_t* count) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_rep) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
+    const uint64_t nseg = c->rp_nseg;
+    if (first && nseg) HIP_OR(hipMemcpyAsync(first, c->rp_first.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (count && nseg) HIP_OR(hipMemcpyAsync(count, c->rp_count.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+int hvws_get_reply_flags(hvws_ctx* c, uint8_t* out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_rep) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
+    const uint64_t nseg = c->rp_nseg;
+    if (out && nseg) HIP_OR(hipMemcpyAsync(out, c->rp_flags.p, nseg, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
     return HVWS_OK;
 }
 

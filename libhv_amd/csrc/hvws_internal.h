@@ -523,6 +523,37 @@ hipError_t launch_msg_gather(int g, const uint8_t* rx, uint64_t rx_len, const ui
                              const uint32_t* keyrot, const uint64_t* out_off, const uint32_t* tile_first,
                              uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
                              hipStream_t st);
+// Batched send and server replies (hvws_send.hip; include/hvws.h has both
+// contracts).  dtxmsg mirrors hvws_tx_msg.
+struct dtxmsg {
+    uint64_t off, len;
+    uint32_t flags, key;
+};
+enum : uint32_t { R_PONG = 1u, R_CLOSE = 2u, R_ECHO = 4u, RF_CLOSED = 1u, RF_DEFERRED = 2u };
+uint64_t send_scratch_bytes(uint64_t n);
+// The message pass over msgs[0 .. min(*n_dev, n)) (n_dev may be null), F bytes
+// per fragment: scratch (send_scratch_bytes(n)) keeps each message's frames and
+// output bytes before it; first: n + 1 words, each message's first frame;
+// msg_off: the same in output bytes (optional); meta (zeroed by the caller):
+// [0..3] = frames, output bytes, bad messages, effective count, [4] = messages
+// breaking the uniform layout, [5..7] = off[0], off[1] - off[0], len[0].
+hipError_t launch_send_table(const dtxmsg* msgs, uint64_t n, const uint64_t* n_dev, uint64_t plen, uint64_t F,
+                             int masked, void* scratch, uint64_t* first, uint64_t* msg_off, uint64_t* meta,
+                             hipStream_t st);
+// One thread per frame (nframes = meta[0], read by the host): the rows
+// launch_tx_index / launch_build take.
+hipError_t launch_send_expand(const dtxmsg* msgs, const void* scratch, const uint64_t* first, const uint64_t* meta,
+                              uint64_t nframes, uint64_t F, int masked, uint64_t* pay_off, uint64_t* len,
+                              uint8_t* flags, uint32_t* mask, uint64_t* out_off, uint64_t* size, hipStream_t st);
+// The reply rule over hvws_messages' piece table (msgs, mg_meta[2] pieces
+// clamped to cap, per-segment seg_first / seg_count).  closed_in: device, nseg
+// bytes or null; limit: nseg words; scratch: rep_scratch_words(cap) words, of
+// which word `cap` receives the reply count; out / piece: cap entries.
+uint64_t rep_scratch_words(uint64_t cap);
+hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t cap, const uint64_t* seg_first,
+                          const uint64_t* seg_count, uint32_t nseg, uint32_t policy, const uint8_t* closed_in,
+                          uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
+                          uint64_t* rep_count, uint8_t* flags, hipStream_t st);
 // Predicted frames above which a uniform segment is verified grid-wide (k_verify).
 uint64_t spec_min();
 uint64_t set_spec_min(uint64_t v);   // 0 = default; returns the previous value
