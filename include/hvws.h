@@ -509,7 +509,8 @@ uint64_t hvws_utf8_tile(void);
  *   - a state_in with open == 0 and pending != 0, or with opcode > 15, is
  *     HVWS_EINVAL.
  * Concatenating a message's pieces across batches is the caller's: the piece
- * with HVWS_M_END gives the message's length in `total`. */
+ * with HVWS_M_END gives the message's length in `total`.  (hvws_messages_joined,
+ * below, does it on the device.) */
 typedef struct hvws_msg_state {   /* 16 B per connection; all zero = fresh */
     uint64_t pending;             /* bytes of the open message delivered in earlier batches' pieces */
     uint32_t opcode;              /* latched opcode, 0 = none latched yet */
@@ -564,6 +565,66 @@ const hvws_msg* hvws_messages_device(hvws_ctx* ctx);
  * (tests place record boundaries around its multiples).  Results never depend
  * on the geometry. */
 uint64_t hvws_msg_tile(void);
+
+/* ---- whole messages across batches ---------------------------------------- */
+/* hvws_messages with the bytes of every connection's open message kept on the
+ * device between batches, so that every piece with HVWS_M_END is the complete
+ * message, contiguous in d_out, and hvws_replies / hvws_send_messages answer
+ * it with no host copy (no segment is HVWS_RF_DEFERRED).  The library keeps no
+ * per-connection memory: the previous call's output is the pending store.  The
+ * caller alternates two (or more) output buffers; the trailing open piece a
+ * batch leaves for a connection is a byte range of that batch's d_out, and the
+ * next batch copies that range (already unmasked, copied as it is) to the front
+ * of the connection's part of the new d_out and appends the new payload bytes.
+ * A connection with an open message and no read in a batch is passed as a
+ * segment of length 0 -- its bytes are carried forward -- or, by a caller that
+ * keeps older output buffers alive, left out of the batch.
+ *
+ * Everything hvws_messages documents holds (the preconditions on the scan,
+ * d_rx and masked, the records of a RUN step, asynchrony, hvws_last_kernel_ms,
+ * all getters, hvws_replies afterwards) except, with P[s] = state_in[s].pending
+ * (0 when state_in is NULL):
+ *   Carried bytes.  prev_off: host, nseg words; segment s's carried bytes are
+ *     d_prev[prev_off[s] .. prev_off[s] + P[s]); prev_off[s] is ignored when
+ *     P[s] == 0.  d_prev and prev_off may be NULL only when every P[s] is 0.
+ *     d_prev must be 16-byte aligned; ranges may start at any byte and may
+ *     overlap each other.  HVWS_EINVAL, nothing written: a pending byte without
+ *     d_prev or prev_off; a range outside [0, prev_len); d_out[0, out_cap)
+ *     overlapping d_rx[0, rx_len) or d_prev[0, prev_len).  No read leaves
+ *     [d_prev, d_prev + prev_len) or the batch.
+ *   Output.  Segments are in order; segment s's part of d_out is its P[s]
+ *     carried bytes, then its records' payload bytes as hvws_messages lays
+ *     them out; record r's bytes start at the sum of all carried and payload
+ *     bytes before it.  hvws_msg_bytes is the sum of P[s] plus the payload
+ *     bytes; no byte of d_out at or beyond that total is written.
+ *   Pieces.  The rule is unchanged, but the first piece of a segment with
+ *     P[s] > 0 starts at the segment's carried bytes and its len includes
+ *     them: total == len for every piece.  HVWS_M_CONT, the opcode, rec and
+ *     seg are as in hvws_messages.  A segment without records and with
+ *     P[s] > 0 has exactly one piece: open, len = total = P[s], rec =
+ *     HVWS_MSG_NOREC, opcode bits state_in[s].opcode (8 when that is 0),
+ *     HVWS_M_CONT set; with P[s] == 0 it has none.  The table may hold up to
+ *     nseg pieces more than the batch has records.  state_out equals what
+ *     hvws_messages returns for the same inputs.
+ *   out_cap.  No wait when out_cap >= rx_len + the sum of P[s] (saturating);
+ *     otherwise one wait for the total, and HVWS_EINVAL with nothing written if
+ *     it does not fit.
+ * With every P[s] == 0 the bytes, tables, states and counts equal
+ * hvws_messages' exactly.  hvws_replies after it runs unchanged; the
+ * HVWS_MSG_NOREC piece has no HVWS_M_END, so it selects and indexes nothing.
+ *
+ * Cost: a message of L bytes delivered over k batches is copied about k*L/2
+ * bytes in total.
+ *
+ * hvws_get_msg_carry (waits): off[s] = the offset in this call's d_out of
+ * segment s's trailing open piece -- the connection's prev_off in its next
+ * batch -- and 0 when state_out[s].pending == 0.  HVWS_EINVAL after a plain
+ * hvws_messages. */
+#define HVWS_MSG_NOREC UINT64_MAX
+int hvws_messages_joined(hvws_ctx* ctx, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out,
+                         uint64_t out_cap, const hvws_msg_state* state_in, const uint8_t* d_prev, uint64_t prev_len,
+                         const uint64_t* prev_off);
+int hvws_get_msg_carry(hvws_ctx* ctx, uint64_t* off);
 
 /* ---- batched send, device resident ---------------------------------------- */
 /* WebSocketChannel::send (http/WebSocketChannel.cpp:5-48) for n messages at

@@ -172,6 +172,12 @@ _SIGS = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
          ctypes.c_void_p],
     ),
+    "hvws_messages_joined": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "hvws_get_msg_carry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_msg_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "hvws_msg_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "hvws_get_messages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
@@ -549,6 +555,31 @@ class Engine:
             st = np.ascontiguousarray(state_in, dtype=MSG_STATE_DTYPE)
         _check(lib().hvws_messages(self.ctx, rx.ptr, rx_len, int(bool(masked)), out.ptr, out_cap,
                                    st.ctypes.data if st is not None else None), "hvws_messages")
+
+    def messages_joined(self, rx: DeviceBuffer, rx_len: int, masked: bool, out: DeviceBuffer, out_cap: int,
+                        state_in=None, prev=None, prev_len: int = 0, prev_off=None) -> None:
+        """hvws_messages_joined: messages() with each segment's state_in.pending
+        carried bytes, prev[prev_off[s] ..) of the previous call's output, copied
+        ahead of the segment's payload bytes, so that every M_END piece is a whole
+        message in `out`.  prev: a DeviceBuffer or a device address; prev_off: one
+        offset per segment (both None = nothing pending)."""
+        st = None
+        if state_in is not None:
+            st = np.ascontiguousarray(state_in, dtype=MSG_STATE_DTYPE)
+        po = None
+        if prev_off is not None:
+            po = np.ascontiguousarray(prev_off, dtype=np.uint64)
+        pp = prev.ptr if hasattr(prev, "ptr") else prev
+        _check(lib().hvws_messages_joined(self.ctx, rx.ptr, rx_len, int(bool(masked)), out.ptr, out_cap,
+                                          st.ctypes.data if st is not None else None, pp, prev_len,
+                                          po.ctypes.data if po is not None else None), "hvws_messages_joined")
+
+    def msg_carry(self, nseg: int) -> np.ndarray:
+        """Per segment of the last messages_joined() call, the offset in its output
+        of the trailing open piece: the connection's prev_off in its next batch."""
+        out = np.zeros(max(nseg, 1), dtype=np.uint64)
+        _check(lib().hvws_get_msg_carry(self.ctx, out.ctypes.data), "hvws_get_msg_carry")
+        return out[:nseg]
 
     def message_table(self) -> np.ndarray:
         """The pieces of the last messages() call (MSG_DTYPE)."""

@@ -258,7 +258,12 @@ struct hvws_ctx {
     bool mg_up_pending = false;
     bool have_msg = false;
     uint32_t mg_nseg = 0;
-    uint64_t mg_cap = 0;   // the piece bound of the last hvws_messages (its record capacity)
+    uint64_t mg_cap = 0;   // the piece bound of the last hvws_messages (its record capacity; joined: its rows)
+    // hvws_messages_joined: the row table (length, source, key, info per row),
+    // each piece's last row, each segment's carry offset; prev_off goes up
+    // behind state_in in the same slot
+    dbuf mj_len, mj_src, mj_key, mj_info, mj_prow, mj_carry;
+    bool have_join = false;   // the last hvws_messages was the joined form
     // hvws_send_messages: the message scan's scratch, each message's first
     // frame, {frames, bytes, bad, count, uniform layout}, and the per-frame rows
     // k_build reads (out_off and size in tx_off / tx_size)
@@ -2301,7 +2306,8 @@ void hvws_ctx_destroy(hvws_ctx* c) {
                         &c->tx_size, &c->tx_off, &c->tx_scan, &c->tx_tiles, &c->tx_stat, &c->tx_span, &c->d_small_in,
                         &c->d_small_slots, &c->u8_words, &c->u8_flags, &c->u8_tiles, &c->u8_meta, &c->u8_in, &c->u8_out,
                         &c->u8_bad, &c->mg_scan, &c->mg_off, &c->mg_tiles, &c->mg_msgs, &c->mg_first, &c->mg_count,
-                        &c->mg_in, &c->mg_out, &c->mg_meta, &c->sd_scan, &c->sd_first, &c->sd_meta, &c->sd_poff,
+                        &c->mg_in, &c->mg_out, &c->mg_meta, &c->mj_len, &c->mj_src, &c->mj_key, &c->mj_info, &c->mj_prow,
+                        &c->mj_carry, &c->sd_scan, &c->sd_first, &c->sd_meta, &c->sd_poff,
                         &c->sd_len, &c->sd_flags, &c->sd_mask, &c->rp_scan, &c->rp_limit, &c->rp_msgs, &c->rp_piece,
                         &c->rp_first, &c->rp_count, &c->rp_flags, &c->rp_closed})
             b->release();
@@ -2685,9 +2691,19 @@ static_assert(M_END == HVWS_M_END && M_CONT == HVWS_M_CONT, "piece bits");
 // Message reassembly over the last scan's frame table (hvws_msg.hip): the
 // table pass, the tile index over the output, the gather -- all on the context
 // stream, behind the scan (and the unmask of a step), reading rx and the
-// current table set only.
-int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
-                  const hvws_msg_state* state_in) {
+// current table set only.  prev != nullptr: the joined form
+// (hvws_messages_joined), whose tables are over rows -- per segment its carried
+// span in prev->d, then its records -- and which may run with up to nseg pieces
+// more than records.
+namespace {
+struct msg_prev {
+    const uint8_t* d;
+    uint64_t len;
+    const uint64_t* off;   // host, nseg words
+};
+
+int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
+                  const hvws_msg_state* state_in, const msg_prev* prev) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_messages without a preceding hvws_scan");
@@ -2704,45 +2720,99 @@ int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         for (uint32_t s = 0; s < nseg; ++s)
             if ((state_in[s].open == 0 && state_in[s].pending != 0) || state_in[s].opcode > 15)
                 return set_err(HVWS_EINVAL, "hvws_messages: state_in is no state hvws_get_msg_state returns");
+    // The joined form: every carried range inside prev, the output clear of it;
+    // carried = the sum of the pending bytes, saturating.
+    uint64_t carried = 0;
+    if (prev) {
+        if (((uintptr_t)prev->d & 15u) != 0)
+            return set_err(HVWS_EINVAL, "hvws_messages_joined: d_prev must be 16-byte aligned");
+        if (state_in)
+            for (uint32_t s = 0; s < nseg; ++s) {
+                const uint64_t P = state_in[s].pending;
+                if (P == 0) continue;
+                if (!prev->d || !prev->off)
+                    return set_err(HVWS_EINVAL, "hvws_messages_joined: pending bytes without d_prev / prev_off");
+                if (prev->off[s] > prev->len || P > prev->len - prev->off[s])
+                    return set_err(HVWS_EINVAL, "hvws_messages_joined: a carried range leaves d_prev");
+                carried = P > UINT64_MAX - carried ? UINT64_MAX : carried + P;
+            }
+        const uintptr_t o = (uintptr_t)d_out, p = (uintptr_t)prev->d;
+        if (prev->d && o < p + prev->len && p < o + out_cap)
+            return set_err(HVWS_EINVAL, "hvws_messages_joined: d_out overlaps d_prev");
+    }
+    const bool rows = prev && nseg;   // without segments there is no carried row: the plain tables
     // a RUN step left no frame table: build it now (as hvws_unmask does)
     if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
     // c->nfr: the record count, or its bound while the count is on the device
     const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
-    const uint64_t bound = std::min(rx_len, out_cap);   // the payload cannot exceed the batch
-    const int geom = msg_variant(rx_len, cap);
+    const uint64_t ncap = rows ? cap + nseg : cap;   // rows, and the bound of the pieces
+    // the output cannot exceed the batch and what is carried
+    const uint64_t need = carried > UINT64_MAX - rx_len ? UINT64_MAX : rx_len + carried;
+    const uint64_t bound = std::min(need, out_cap);
+    const int geom = msg_variant(need, cap);
     const uint64_t tile = msg_gather_tile(geom);
     uint64_t ntiles = (bound + tile - 1) / tile;
-    HIP_OR(c->mg_scan.ensure(msg_scratch_bytes(cap)), HVWS_ENOMEM);
-    HIP_OR(c->mg_off.ensure(cap * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_scan.ensure(msg_scratch_bytes(ncap)), HVWS_ENOMEM);
+    HIP_OR(c->mg_off.ensure(ncap * 8 + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
-    HIP_OR(c->mg_msgs.ensure((cap + 1) * sizeof(dmsg)), HVWS_ENOMEM);
+    HIP_OR(c->mg_msgs.ensure((ncap + 1) * sizeof(dmsg)), HVWS_ENOMEM);
     HIP_OR(c->mg_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_in.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
+    // state_in, then (joined) prev_off
+    HIP_OR(c->mg_in.ensure((uint64_t)nseg * (sizeof(dmsg_state) + 8) + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_out.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_meta.ensure(64), HVWS_ENOMEM);
+    if (rows) {
+        HIP_OR(c->mj_len.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mj_src.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mj_key.ensure(ncap * 4 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mj_info.ensure(ncap * 4 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mj_prow.ensure((ncap + 1) * 8), HVWS_ENOMEM);
+        HIP_OR(c->mj_carry.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    }
     c->have_msg = false;   // the tables are being rewritten
+    c->have_join = false;
     c->have_rep = false;   // ... which a reply table indexes
+    const bool with_off = rows && carried;   // prev_off rides behind the states in the same slot
     if (state_in && nseg) {
-        const uint64_t bytes = (uint64_t)nseg * sizeof(dmsg_state);
+        const uint64_t sbytes = (uint64_t)nseg * sizeof(dmsg_state);
+        const uint64_t bytes = sbytes + (with_off ? (uint64_t)nseg * 8 : 0);
         if (!c->mg_up_ev) HIP_OR(hipEventCreateWithFlags(&c->mg_up_ev, hipEventDisableTiming), HVWS_EHIP);
         if (c->mg_up_pending) {   // the previous pass's copy out of the slot
             HIP_OR(hipEventSynchronize(c->mg_up_ev), HVWS_EHIP);
             c->mg_up_pending = false;
         }
         HIP_OR(c->h_mg_in.ensure(bytes), HVWS_ENOMEM);
-        memcpy(c->h_mg_in.p, state_in, bytes);
+        memcpy(c->h_mg_in.p, state_in, sbytes);
+        if (with_off) memcpy((uint8_t*)c->h_mg_in.p + sbytes, prev->off, (uint64_t)nseg * 8);
         HIP_OR(hipMemcpyAsync(c->mg_in.p, c->h_mg_in.p, bytes, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
         HIP_OR(hipEventRecord(c->mg_up_ev, c->stream), HVWS_EHIP);
         c->mg_up_pending = true;
     }
+    const msg_rows mr{c->mj_len.as<uint64_t>(), c->mj_src.as<uint64_t>(), c->mj_key.as<uint32_t>(),
+                      c->mj_info.as<uint32_t>(), c->mj_prow.as<uint64_t>()};
     HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
-    HIP_OR(launch_msg_table(c->T().f_len.as<uint64_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(), cap,
-                            c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), nseg,
-                            state_in ? c->mg_in.as<dmsg_state>() : nullptr, c->mg_scan.p, c->mg_off.as<uint64_t>(),
-                            c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
-                            c->mg_out.as<dmsg_state>(), c->mg_meta.as<uint64_t>(), c->stream),
-           HVWS_EHIP);
+    if (rows) {
+        const dframes fr{nullptr, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), nullptr, nullptr,
+                         c->T().f_keyrot.as<uint32_t>(), c->T().f_info.as<uint32_t>(), cap};
+        const uint64_t* d_prev_off =
+            with_off ? reinterpret_cast<const uint64_t*>((uint8_t*)c->mg_in.p + (uint64_t)nseg * sizeof(dmsg_state))
+                     : nullptr;
+        HIP_OR(launch_msg_table_joined(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().counts.as<uint64_t>(),
+                                       c->T().bases.as<uint64_t>(), nseg,
+                                       state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p, mr,
+                                       c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(),
+                                       c->mg_count.as<uint64_t>(), c->mg_out.as<dmsg_state>(),
+                                       c->mj_carry.as<uint64_t>(), c->mg_meta.as<uint64_t>(), c->stream),
+               HVWS_EHIP);
+    } else {
+        HIP_OR(launch_msg_table(c->T().f_len.as<uint64_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(),
+                                cap, c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), nseg,
+                                state_in ? c->mg_in.as<dmsg_state>() : nullptr, c->mg_scan.p, c->mg_off.as<uint64_t>(),
+                                c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
+                                c->mg_out.as<dmsg_state>(), c->mg_meta.as<uint64_t>(), c->stream),
+               HVWS_EHIP);
+    }
     // Pipelined steps: the scan two steps on writes this table set and must
     // wait for this pass as it waits for the set's unmask.
     auto free_event = [&]() -> int {
@@ -2754,7 +2824,7 @@ int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         return HVWS_OK;
     };
     bool fits = true;
-    if (out_cap < rx_len) {   // the one wait: does the payload fit?
+    if (out_cap < need) {   // the one wait: does the payload fit?
         uint64_t total = 0;
         HIP_OR(hipMemcpyAsync(&total, c->mg_meta.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
         HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
@@ -2762,22 +2832,54 @@ int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         ntiles = (std::min(total, out_cap) + tile - 1) / tile;
     }
     if (fits) {
+        // the tile index over the output: by records, or by rows (meta[0] counts either)
         if (ntiles)
-            HIP_OR(launch_tile_index(c->mg_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), 0, c->mg_meta.as<uint64_t>(),
-                                     c->mg_tiles.as<uint32_t>(), ntiles, tile, c->stream),
+            HIP_OR(launch_tile_index(c->mg_off.as<uint64_t>(), rows ? mr.len : c->T().f_len.as<uint64_t>(), 0,
+                                     c->mg_meta.as<uint64_t>(), c->mg_tiles.as<uint32_t>(), ntiles, tile, c->stream),
                    HVWS_EHIP);
-        HIP_OR(launch_msg_gather(geom, d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
-                                 c->T().f_keyrot.as<uint32_t>(), c->mg_off.as<uint64_t>(), c->mg_tiles.as<uint32_t>(),
-                                 ntiles, c->mg_meta.as<uint64_t>(), masked, d_out, out_cap, c->stream),
-               HVWS_EHIP);
+        if (rows)
+            HIP_OR(launch_msg_gather_joined(geom, d_rx, rx_len, prev->d, prev->d ? prev->len : 0, mr,
+                                            c->mg_off.as<uint64_t>(), c->mg_tiles.as<uint32_t>(), ntiles,
+                                            c->mg_meta.as<uint64_t>(), masked, d_out, out_cap, c->stream),
+                   HVWS_EHIP);
+        else
+            HIP_OR(launch_msg_gather(geom, d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
+                                     c->T().f_keyrot.as<uint32_t>(), c->mg_off.as<uint64_t>(),
+                                     c->mg_tiles.as<uint32_t>(), ntiles, c->mg_meta.as<uint64_t>(), masked, d_out,
+                                     out_cap, c->stream),
+                   HVWS_EHIP);
     }
     HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
     c->ev_build = true;
     if ((rc = free_event()) != HVWS_OK) return rc;
     if (!fits) return set_err(HVWS_EINVAL, "hvws_messages: the payload does not fit out_cap");
     c->have_msg = true;
+    c->have_join = prev != nullptr;
     c->mg_nseg = nseg;
-    c->mg_cap = cap;
+    c->mg_cap = ncap;
+    return HVWS_OK;
+}
+}  // namespace
+
+int hvws_messages(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
+                  const hvws_msg_state* state_in) {
+    return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in, nullptr);
+}
+
+int hvws_messages_joined(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out,
+                         uint64_t out_cap, const hvws_msg_state* state_in, const uint8_t* d_prev, uint64_t prev_len,
+                         const uint64_t* prev_off) {
+    const msg_prev prev{d_prev, d_prev ? prev_len : 0, prev_off};
+    return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in, &prev);
+}
+
+int hvws_get_msg_carry(hvws_ctx* c, uint64_t* off) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg || !c->have_join) return set_err(HVWS_EINVAL, "no hvws_messages_joined call yet");
+    const uint64_t nseg = c->mg_nseg;
+    if (off && nseg) HIP_OR(hipMemcpyAsync(off, c->mj_carry.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
     return HVWS_OK;
 }
 

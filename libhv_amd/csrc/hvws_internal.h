@@ -523,6 +523,34 @@ hipError_t launch_msg_gather(int g, const uint8_t* rx, uint64_t rx_len, const ui
                              const uint32_t* keyrot, const uint64_t* out_off, const uint32_t* tile_first,
                              uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
                              hipStream_t st);
+// The joined form (hvws_messages_joined): both passes over rows -- per segment
+// its carried span, then its records; cap + nseg of them.  len / src / key /
+// info: the row table k_join_rows writes; prow: each piece's last row (rows + 1
+// words).  All device memory.
+struct msg_rows {
+    uint64_t* len;
+    uint64_t* src;
+    uint32_t* key;
+    uint32_t* info;
+    uint64_t* prow;
+};
+// launch_msg_table over rows: fr's pay_off / pay_len / keyrot / info are read;
+// scratch: msg_scratch_bytes(cap + nseg); out_off: cap + nseg words; msgs:
+// cap + nseg + 1 entries; state_in and prev_off (device, nseg entries) may be
+// null when nothing is pending; carry_off: nseg words; meta[0..2] = rows, bytes
+// (carried and payload), pieces.  nseg > 0.
+hipError_t launch_msg_table_joined(const dframes& fr, int masked, const uint64_t* nfr_dev, uint64_t cap,
+                                   const uint64_t* counts, const uint64_t* bases, uint32_t nseg,
+                                   const dmsg_state* state_in, const uint64_t* prev_off, void* scratch,
+                                   const msg_rows& rows, uint64_t* out_off, dmsg* msgs, uint64_t* seg_first,
+                                   uint64_t* seg_count, dmsg_state* state_out, uint64_t* carry_off, uint64_t* meta,
+                                   hipStream_t st);
+// launch_msg_gather over rows: tile_first is launch_tile_index over (out_off,
+// rows.len, meta).  No read leaves [rx, rx + rx_len) or [prev, prev + prev_len).
+hipError_t launch_msg_gather_joined(int g, const uint8_t* rx, uint64_t rx_len, const uint8_t* prev, uint64_t prev_len,
+                                    const msg_rows& rows, const uint64_t* out_off, const uint32_t* tile_first,
+                                    uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
+                                    hipStream_t st);
 // Batched send and server replies (hvws_send.hip; include/hvws.h has both
 // contracts).  dtxmsg mirrors hvws_tx_msg.
 struct dtxmsg {

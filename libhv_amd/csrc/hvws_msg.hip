@@ -34,6 +34,15 @@
 // Traffic: payload read + payload written + ~100 bytes per record of tables.
 // No source read leaves [rx, rx + rx_len); no byte at or beyond
 // min(payload total, out_cap) is written.
+//
+// The joined form (hvws_messages_joined) runs the same two parts over ROWS:
+// each segment's carried span -- the bytes of its open message, lying in the
+// previous call's output -- is a row ahead of the segment's records, so row
+// b(s) = min(bases[s], records) + s is segment s's carried row and record r of
+// segment s is row r + s + 1.  k_join_rows writes the row table once (length,
+// source with a buffer selector, key, info with the piece-closing bit); the
+// scan, the three table kernels, the tile index and the gather then take rows
+// where the plain form takes records, and the work stays spread by rows.
 #include <stdlib.h>
 
 #include "hvws_dev.h"
@@ -69,8 +78,13 @@ struct msg_load {
     uint64_t cap;
     const uint64_t* bases;
     uint32_t nseg;
+    static constexpr bool JOINED = false;
     __device__ __forceinline__ uint64_t nrec() const { return *nfr_p < cap ? *nfr_p : cap; }
     __device__ __forceinline__ static bool fin_end(uint32_t inf) { return (inf & I_END) && (inf & F_FIN); }
+    __device__ __forceinline__ uint64_t len(uint64_t r) const { return pay_len[r]; }
+    __device__ __forceinline__ uint32_t inf(uint64_t r) const { return info[r]; }
+    __device__ __forceinline__ uint32_t seg_of(uint64_t r) const { return seg_after(bases, nseg, r) - 1u; }
+    __device__ __forceinline__ uint64_t base(uint32_t s) const { return bases[s]; }
     __device__ __forceinline__ msg3 operator()(uint64_t r) const {
         const uint64_t n = nrec();
         if (r >= n) return msg3{};
@@ -85,6 +99,83 @@ struct msg_load {
     }
 };
 
+// ---- the joined form's rows
+constexpr uint64_t ROW_PREV = 1ull << 63;   // a row's source word: an offset into prev, not rx
+constexpr uint32_t ROW_CLOSE = 1u << 31;    // a row's info: it closes a piece (the frame info ends below bit 24)
+
+// Rows where msg_load has records.  nrec() counts rows; a row's info is its
+// record's (0 for a carried row) with ROW_CLOSE worked out by k_join_rows.
+struct row_load {
+    const uint64_t* row_len;
+    const uint32_t* row_info;
+    const uint64_t* nfr_p;
+    uint64_t cap;   // records
+    const uint64_t* bases;
+    uint32_t nseg;
+    static constexpr bool JOINED = true;
+    __device__ __forceinline__ uint64_t records() const { return *nfr_p < cap ? *nfr_p : cap; }
+    __device__ __forceinline__ uint64_t nrec() const { return records() + nseg; }
+    __device__ __forceinline__ static bool fin_end(uint32_t inf) { return (inf & I_END) && (inf & F_FIN); }
+    __device__ __forceinline__ uint64_t len(uint64_t i) const { return row_len[i]; }
+    __device__ __forceinline__ uint32_t inf(uint64_t i) const { return row_info[i]; }
+    // segment s's carried row (a table cut short by its capacity leaves later segments without records)
+    __device__ __forceinline__ uint64_t base(uint32_t s) const {
+        const uint64_t n = records(), b = bases[s];
+        return (b < n ? b : n) + s;
+    }
+    // the last segment whose carried row is at or before row i (nseg > 0: row 0 is segment 0's)
+    __device__ __forceinline__ uint32_t seg_of(uint64_t i) const {
+        uint32_t lo = 0, hi = nseg;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (base(mid) > i) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo - 1u;
+    }
+    __device__ __forceinline__ msg3 operator()(uint64_t i) const {
+        if (i >= nrec()) return msg3{};
+        const uint32_t inf = row_info[i];
+        const uint64_t latch = (inf & I_HDR) && (inf & F_OPMASK) ? i + 1 : 0;
+        return msg3{row_len[i], inf & ROW_CLOSE ? 1u : 0u, latch};
+    }
+};
+
+// The row table, one thread per row.  A carried row: P = state_in[s].pending
+// bytes at prev_off[s] of prev, no key; it closes a piece only when the segment
+// has no records and P > 0 (the piece without a record).  A record's row: the
+// record's source, key and info; it closes a piece when a FIN frame ends at it
+// or when it is its segment's last.
+__global__ __launch_bounds__(256) void k_join_rows(row_load in, const uint64_t* __restrict__ pay_off,
+                                                   const uint64_t* __restrict__ pay_len,
+                                                   const uint32_t* __restrict__ info,
+                                                   const uint32_t* __restrict__ keyrot, uint32_t masked,
+                                                   const dmsg_state* __restrict__ state_in,
+                                                   const uint64_t* __restrict__ prev_off,
+                                                   uint64_t* __restrict__ row_len, uint64_t* __restrict__ row_src,
+                                                   uint32_t* __restrict__ row_key, uint32_t* __restrict__ row_info) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t rows = in.nrec();
+    if (i >= rows) return;
+    const uint32_t s = in.seg_of(i);
+    const uint64_t b = in.base(s);
+    const bool last = i + 1 == (s + 1 < in.nseg ? in.base(s + 1) : rows);   // its segment's last row
+    if (i == b) {
+        const uint64_t P = state_in ? state_in[s].pending : 0;
+        row_len[i] = P;
+        row_src[i] = P ? ROW_PREV | prev_off[s] : 0;
+        row_key[i] = 0;
+        row_info[i] = last && P ? ROW_CLOSE : 0u;
+    } else {
+        const uint64_t r = i - s - 1;
+        const uint32_t inf = info[r];
+        row_len[i] = pay_len[r];
+        row_src[i] = pay_off[r];
+        row_key[i] = masked ? keyrot[r] : 0u;
+        row_info[i] = inf | (row_load::fin_end(inf) || last ? ROW_CLOSE : 0u);
+    }
+}
+
 // The scan's result for record r: its block-relative value and its block's base.
 struct msg_scan {
     const msg3* ex;
@@ -95,10 +186,13 @@ struct msg_scan {
     }
 };
 
-// meta[0] = records, meta[1] = payload bytes, meta[2] = pieces
-__global__ __launch_bounds__(256) void k_msg_records(msg_load in, msg_scan sc, const msg3* __restrict__ total,
+// meta[0] = records, meta[1] = payload bytes, meta[2] = pieces.  Joined:
+// meta[0] = rows, meta[1] includes the carried bytes, and each piece's last
+// row goes to prow (msgs[].rec is then another number than the one read here).
+template <typename LOAD>
+__global__ __launch_bounds__(256) void k_msg_records(LOAD in, msg_scan sc, const msg3* __restrict__ total,
                                                      uint64_t* __restrict__ out_off, dmsg* __restrict__ msgs,
-                                                     uint64_t* __restrict__ meta) {
+                                                     uint64_t* __restrict__ prow, uint64_t* __restrict__ meta) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t n = in.nrec();
     if (r == 0) {
@@ -109,37 +203,49 @@ __global__ __launch_bounds__(256) void k_msg_records(msg_load in, msg_scan sc, c
     if (r >= n) return;
     const msg3 e = sc(r);
     out_off[r] = e.bytes;
-    if (in(r).close) msgs[e.close].rec = r;
+    if (in(r).close) {
+        if constexpr (LOAD::JOINED) prow[e.close] = r;
+        else msgs[e.close].rec = r;
+    }
 }
 
-__global__ __launch_bounds__(256) void k_msg_pieces(msg_load in, msg_scan sc, const msg3* __restrict__ total,
+template <typename LOAD>
+__global__ __launch_bounds__(256) void k_msg_pieces(LOAD in, msg_scan sc, const msg3* __restrict__ total,
                                                     const dmsg_state* __restrict__ state_in,
-                                                    dmsg* __restrict__ msgs) {
+                                                    const uint64_t* __restrict__ prow, dmsg* __restrict__ msgs) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= total->close) return;
-    const uint64_t r = msgs[p].rec;
+    uint64_t r;
+    if constexpr (LOAD::JOINED) r = prow[p];
+    else r = msgs[p].rec;
     const msg3 e = sc(r);
     uint64_t off = 0, rp = 0;
     if (p) {
-        rp = msgs[p - 1].rec;
-        off = sc(rp).bytes + in.pay_len[rp];
+        if constexpr (LOAD::JOINED) rp = prow[p - 1];
+        else rp = msgs[p - 1].rec;
+        off = sc(rp).bytes + in.len(rp);
     }
-    const uint32_t seg = seg_after(in.bases, in.nseg, r) - 1u;
-    const uint64_t b = in.bases[seg];
+    const uint32_t seg = in.seg_of(r);
+    const uint64_t b = in.base(seg);   // joined: the carried row, below every latch of the segment
     const bool first = p == 0 || rp < b;   // the segment's first piece
     dmsg_state st = dmsg_state{0, 0, 0};
     if (state_in) st = state_in[seg];
-    const uint32_t inf = in.info[r];
+    const uint32_t inf = in.inf(r);
     const msg3 own = in(r);
     const uint64_t latch = e.latch > own.latch ? e.latch : own.latch;
-    const uint32_t op = latch > b ? in.info[latch - 1] & F_OPMASK : (st.opcode ? st.opcode : 8u);
+    const uint32_t op = latch > b ? in.inf(latch - 1) & F_OPMASK : (st.opcode ? st.opcode : 8u);
     dmsg m;
     m.off = off;
-    m.len = e.bytes + own.bytes - off;
-    m.total = m.len + (first ? st.pending : 0);
-    m.rec = r;
+    m.len = e.bytes + own.bytes - off;   // joined: the first piece's rows begin with the carried one
+    if constexpr (LOAD::JOINED) {
+        m.total = m.len;
+        m.rec = r == b ? ~0ull : r - seg - 1;   // a carried row closes the piece without a record
+    } else {
+        m.total = m.len + (first ? st.pending : 0);
+        m.rec = r;
+    }
     m.seg = seg;
-    m.info = op | (msg_load::fin_end(inf) ? M_END : 0u) | (first && st.open ? M_CONT : 0u);
+    m.info = op | (LOAD::fin_end(inf) ? M_END : 0u) | (first && st.open ? M_CONT : 0u);
     msgs[p] = m;
 }
 
@@ -179,6 +285,50 @@ __global__ __launch_bounds__(256) void k_msg_segs(msg_load in, msg_scan sc, cons
         o.pending = msgs[e.close].total;
     }
     state_out[s] = o;
+}
+
+// k_msg_segs over rows; carry_off[s]: where the segment's trailing open piece
+// begins in the output (0 when nothing is pending).
+__global__ __launch_bounds__(256) void k_join_segs(row_load in, msg_scan sc, const uint64_t* __restrict__ counts,
+                                                   const dmsg_state* __restrict__ state_in,
+                                                   const dmsg* __restrict__ msgs, uint64_t* __restrict__ seg_first,
+                                                   uint64_t* __restrict__ seg_count, dmsg_state* __restrict__ state_out,
+                                                   uint64_t* __restrict__ carry_off) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= in.nseg) return;
+    const uint64_t nrec = in.records();
+    const uint64_t rb = in.bases[s];
+    uint64_t cnt = counts[s];
+    if (rb >= nrec) cnt = 0;
+    else if (cnt > nrec - rb) cnt = nrec - rb;
+    dmsg_state st = dmsg_state{0, 0, 0};
+    if (state_in) st = state_in[s];
+    const uint64_t b = in.base(s);
+    const uint64_t first = sc(b).close;
+    seg_first[s] = first;
+    if (cnt == 0) {   // no records: the state unchanged; carried bytes are one open piece
+        seg_count[s] = st.pending ? 1 : 0;
+        state_out[s] = st;
+        carry_off[s] = st.pending ? msgs[first].off : 0;
+        return;
+    }
+    const uint64_t last = b + cnt;
+    const msg3 e = sc(last), own = in(last);
+    seg_count[s] = e.close + 1 - first;   // the last row closes a piece
+    const uint64_t latch = e.latch > own.latch ? e.latch : own.latch;
+    dmsg_state o;
+    o.opcode = latch > b ? in.inf(latch - 1) & F_OPMASK : st.opcode;
+    uint64_t off = 0;
+    if (row_load::fin_end(in.inf(last))) {
+        o.open = 0;
+        o.pending = 0;
+    } else {   // the trailing open piece: its len holds the carried bytes when it is the only one
+        o.open = 1;
+        o.pending = msgs[e.close].total;
+        if (o.pending) off = msgs[e.close].off;
+    }
+    state_out[s] = o;
+    carry_off[s] = off;
 }
 
 // ------------------------------------------------------------ k_msg_gather
@@ -229,10 +379,27 @@ __device__ __forceinline__ uint32_t msg_find(uint64_t c, uint32_t nf, END endf) 
 // Output chunk [c, c + 16) from record i on (output offset offf(k), output
 // end endf(k), source offset srcf(k), key word for aligned source words
 // keyf(k)), piece by piece; bytes at or beyond `total` are not written.
-template <typename OFF, typename END, typename SRC, typename KEY>
-__device__ __forceinline__ void msg_walk(const uint8_t* __restrict__ rx, uint64_t rx_len, uint8_t* __restrict__ out,
-                                         uint64_t total, uint64_t c, uint32_t i, uint32_t nf, OFF offf, END endf,
-                                         SRC srcf, KEY keyf) {
+// J (the joined form): a source offset with ROW_PREV lies in prev, and no read
+// leaves [prev, prev + prev_len).
+template <bool J>
+__device__ __forceinline__ const uint8_t* msg_source(const uint8_t* rx, uint64_t rx_len, const uint8_t* prev,
+                                                     uint64_t prev_len, uint64_t& q, uint64_t& bound) {
+    if constexpr (J) {
+        if (q & ROW_PREV) {
+            q &= ~ROW_PREV;
+            bound = prev_len;
+            return prev;
+        }
+    }
+    bound = rx_len;
+    return rx;
+}
+
+template <bool J, typename OFF, typename END, typename SRC, typename KEY>
+__device__ __forceinline__ void msg_walk(const uint8_t* __restrict__ rx, uint64_t rx_len,
+                                         const uint8_t* __restrict__ prev, uint64_t prev_len,
+                                         uint8_t* __restrict__ out, uint64_t total, uint64_t c, uint32_t i, uint32_t nf,
+                                         OFF offf, END endf, SRC srcf, KEY keyf) {
     uint64_t lo = 0, hh = 0;
 #pragma unroll 1
     for (; i < nf; ++i) {
@@ -240,9 +407,11 @@ __device__ __forceinline__ void msg_walk(const uint8_t* __restrict__ rx, uint64_
         if (o >= c + 16) break;
         if (e <= o) continue;   // a record of 0 bytes
         const uint64_t pb = o > c ? o : c, pe = e < c + 16 ? e : c + 16;
-        const uint64_t q = srcf(i) + (pb - o);
+        uint64_t q = srcf(i), bound;
+        const uint8_t* from = msg_source<J>(rx, rx_len, prev, prev_len, q, bound);
+        q += pb - o;
         uint64_t vlo, vhi;
-        ld16_any(rx, rx_len, q, vlo, vhi);
+        ld16_any(from, bound, q, vlo, vhi);
         const uint32_t kw = rotr32(keyf(i), 8u * (uint32_t)(q & 3u));
         const uint64_t kk = (uint64_t)kw | ((uint64_t)kw << 32);
         put_bytes(lo, hh, vlo ^ kk, vhi ^ kk, (uint32_t)(pb - c), (uint32_t)(pe - c));
@@ -260,10 +429,11 @@ __device__ __forceinline__ void msg_walk(const uint8_t* __restrict__ rx, uint64_
 // The chunks of one tile.  Chunks inside one record stream (the loads of all
 // U chunks are issued before the first is used); chunks holding a record
 // boundary, and the batch's last partial chunk, walk their pieces afterwards.
-template <int T, int U, typename OFF, typename END, typename SRC, typename KEY>
-__device__ __forceinline__ void msg_tile(const uint8_t* __restrict__ rx, uint64_t rx_len, uint8_t* __restrict__ out,
-                                         uint64_t total, uint64_t base, uint32_t nf, OFF offf, END endf, SRC srcf,
-                                         KEY keyf) {
+template <int T, int U, bool J, typename OFF, typename END, typename SRC, typename KEY>
+__device__ __forceinline__ void msg_tile(const uint8_t* __restrict__ rx, uint64_t rx_len,
+                                         const uint8_t* __restrict__ prev, uint64_t prev_len,
+                                         uint8_t* __restrict__ out, uint64_t total, uint64_t base, uint32_t nf,
+                                         OFF offf, END endf, SRC srcf, KEY keyf) {
     const uint32_t tid = threadIdx.x;
     u32x4 w[U], x[U];
     uint32_t kw[U], sft[U], first[U];
@@ -279,11 +449,13 @@ __device__ __forceinline__ void msg_tile(const uint8_t* __restrict__ rx, uint64_
         first[i] = j;
         if (j >= nf) continue;
         const uint64_t o = offf(j);
-        const uint64_t q = srcf(j) + (c - o);
-        if (o <= c && c + 16 <= endf(j) && c + 16 <= total && (q & ~15ull) + 32 <= rx_len) {
+        uint64_t q = srcf(j), bound;
+        const uint8_t* from = msg_source<J>(rx, rx_len, prev, prev_len, q, bound);
+        q += c - o;
+        if (o <= c && c + 16 <= endf(j) && c + 16 <= total && (q & ~15ull) + 32 <= bound) {
             fastmask |= 1u << i;
             sft[i] = (uint32_t)(q & 15u);
-            const u32x4* p = reinterpret_cast<const u32x4*>(rx + (q & ~15ull));
+            const u32x4* p = reinterpret_cast<const u32x4*>(from + (q & ~15ull));
             w[i] = p[0];
             if (sft[i]) x[i] = p[1];
             kw[i] = rotr32(keyf(j), 8u * (uint32_t)(q & 3u));
@@ -300,12 +472,16 @@ __device__ __forceinline__ void msg_tile(const uint8_t* __restrict__ rx, uint64_
     for (int i = 0; i < U; ++i) {
         if (((fastmask >> i) & 1u) || first[i] >= nf) continue;
         const uint64_t c = base + ((uint64_t)i * T + tid) * 16u;
-        msg_walk(rx, rx_len, out, total, c, first[i], nf, offf, endf, srcf, keyf);
+        msg_walk<J>(rx, rx_len, prev, prev_len, out, total, c, first[i], nf, offf, endf, srcf, keyf);
     }
 }
 
-template <int G>
+// J: the tables are the row table's (pay_off = the rows' source words, meta[0]
+// = rows); a carried row streams, stages and walks as a record does, from prev.
+// The joined instantiations take 58 and 126 VGPRs, no scratch.
+template <int G, bool J>
 __global__ __launch_bounds__(msg_geom<G>::T) void k_msg_gather(const uint8_t* __restrict__ rx, uint64_t rx_len,
+                                                     const uint8_t* __restrict__ prev, uint64_t prev_len,
                                                      const uint64_t* __restrict__ pay_off,
                                                      const uint64_t* __restrict__ pay_len,
                                                      const uint32_t* __restrict__ keyrot,
@@ -337,13 +513,15 @@ __global__ __launch_bounds__(msg_geom<G>::T) void k_msg_gather(const uint8_t* __
     {
         const uint64_t o = out_off[k0], n = pay_len[k0];
         if (o <= base && base + TILE <= o + n && base + TILE <= total) {
-            const uint64_t src = pay_off[k0] + (base - o);
+            uint64_t src = pay_off[k0], bound;
+            const uint8_t* from = msg_source<J>(rx, rx_len, prev, prev_len, src, bound);
+            src += base - o;
             const uint64_t src_a = src & ~15ull;
             const uint32_t sft = (uint32_t)(src & 15u);
-            if (src_a + TILE + (sft ? 16u : 0u) <= rx_len) {
+            if (src_a + TILE + (sft ? 16u : 0u) <= bound) {
                 const uint32_t kw = masked ? rotr32(keyrot[k0], 8u * (uint32_t)(src & 3u)) : 0u;
                 const u32x4 kv = u32x4{kw, kw, kw, kw};
-                const uint8_t* sp = rx + src_a;
+                const uint8_t* sp = from + src_a;
                 u32x4 v[U];
                 if (sft == 0) {
 #pragma unroll
@@ -372,7 +550,7 @@ __global__ __launch_bounds__(msg_geom<G>::T) void k_msg_gather(const uint8_t* __
 
     auto chunk = [&](uint64_t c, auto offf, auto endf, auto srcf, auto keyf) {
         const uint32_t j = msg_find(c, nf, endf);
-        if (j < nf) msg_walk(rx, rx_len, out, total, c, j, nf, offf, endf, srcf, keyf);
+        if (j < nf) msg_walk<J>(rx, rx_len, prev, prev_len, out, total, c, j, nf, offf, endf, srcf, keyf);
     };
     if (nf <= MAXF) {
         for (uint32_t i = tid; i < nf; i += T) {
@@ -388,7 +566,7 @@ __global__ __launch_bounds__(msg_geom<G>::T) void k_msg_gather(const uint8_t* __
         auto srcf = [&](uint32_t k) { return s_src[k]; };
         auto keyf = [&](uint32_t k) { return s_key[k]; };
         if constexpr (msg_geom<G>::AHEAD) {
-            msg_tile<T, U>(rx, rx_len, out, total, base, nf, offf, endf, srcf, keyf);
+            msg_tile<T, U, J>(rx, rx_len, prev, prev_len, out, total, base, nf, offf, endf, srcf, keyf);
         } else {
 #pragma unroll 1
             for (int i = 0; i < U; ++i) {
@@ -435,11 +613,41 @@ hipError_t launch_msg_table(const uint64_t* pay_len, const uint32_t* info, const
     const uint64_t nb = (cap + SCAN_B - 1) / SCAN_B;
     const msg_scan sc{ex, nb > 1 ? tmp + nb : (const msg3*)nullptr};
     const uint32_t rb = (uint32_t)((cap + 255) / 256);
-    hipLaunchKernelGGL(k_msg_records, dim3(rb ? rb : 1), dim3(256), 0, st, in, sc, total, out_off, msgs, meta);
-    if (rb) hipLaunchKernelGGL(k_msg_pieces, dim3(rb), dim3(256), 0, st, in, sc, total, state_in, msgs);
+    hipLaunchKernelGGL(k_msg_records<msg_load>, dim3(rb ? rb : 1), dim3(256), 0, st, in, sc, total, out_off, msgs,
+                       (uint64_t*)nullptr, meta);
+    if (rb)
+        hipLaunchKernelGGL(k_msg_pieces<msg_load>, dim3(rb), dim3(256), 0, st, in, sc, total, state_in,
+                           (const uint64_t*)nullptr, msgs);
     if (nseg)
         hipLaunchKernelGGL(k_msg_segs, dim3((nseg + 255) / 256), dim3(256), 0, st, in, sc, total, counts, state_in, msgs,
                            seg_first, seg_count, state_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_msg_table_joined(const dframes& fr, int masked, const uint64_t* nfr_dev, uint64_t cap,
+                                   const uint64_t* counts, const uint64_t* bases, uint32_t nseg,
+                                   const dmsg_state* state_in, const uint64_t* prev_off, void* scratch,
+                                   const msg_rows& rows, uint64_t* out_off, dmsg* msgs, uint64_t* seg_first,
+                                   uint64_t* seg_count, dmsg_state* state_out, uint64_t* carry_off, uint64_t* meta,
+                                   hipStream_t st) {
+    if (nseg == 0) return hipErrorInvalidValue;   // row 0 is segment 0's
+    const uint64_t nrows = cap + nseg;
+    msg3* ex = reinterpret_cast<msg3*>(scratch);
+    msg3* total = ex + nrows;
+    msg3* tmp = ex + nrows + 16;
+    const row_load in{rows.len, rows.info, nfr_dev, cap, bases, nseg};
+    const uint32_t rb = (uint32_t)((nrows + 255) / 256);
+    hipLaunchKernelGGL(k_join_rows, dim3(rb), dim3(256), 0, st, in, fr.pay_off, fr.pay_len, fr.info, fr.keyrot,
+                       masked ? 1u : 0u, state_in, prev_off, rows.len, rows.src, rows.key, rows.info);
+    hipError_t e = launch_scan_of(in, ex, nrows, tmp, total, st, false);
+    if (e != hipSuccess) return e;
+    const uint64_t nb = (nrows + SCAN_B - 1) / SCAN_B;
+    const msg_scan sc{ex, nb > 1 ? tmp + nb : (const msg3*)nullptr};
+    hipLaunchKernelGGL(k_msg_records<row_load>, dim3(rb), dim3(256), 0, st, in, sc, total, out_off, msgs, rows.prow,
+                       meta);
+    hipLaunchKernelGGL(k_msg_pieces<row_load>, dim3(rb), dim3(256), 0, st, in, sc, total, state_in, rows.prow, msgs);
+    hipLaunchKernelGGL(k_join_segs, dim3((nseg + 255) / 256), dim3(256), 0, st, in, sc, counts, state_in, msgs,
+                       seg_first, seg_count, state_out, carry_off);
     return hipGetLastError();
 }
 
@@ -455,11 +663,32 @@ hipError_t launch_msg_gather(int g, const uint8_t* rx, uint64_t rx_len, const ui
     for (uint64_t t0 = 0; t0 < ntiles; t0 += per_launch) {
         const uint64_t nt = ntiles - t0 < per_launch ? ntiles - t0 : per_launch;
         if (g == 1)
-            hipLaunchKernelGGL(k_msg_gather<1>, dim3((uint32_t)nt), dim3(msg_geom<1>::T), 0, st, rx, rx_len, pay_off,
-                               pay_len, keyrot, out_off, tile_first, meta, masked ? 1u : 0u, out, out_cap, t0);
+            hipLaunchKernelGGL((k_msg_gather<1, false>), dim3((uint32_t)nt), dim3(msg_geom<1>::T), 0, st, rx, rx_len,
+                               (const uint8_t*)nullptr, (uint64_t)0, pay_off, pay_len, keyrot, out_off, tile_first, meta,
+                               masked ? 1u : 0u, out, out_cap, t0);
         else
-            hipLaunchKernelGGL(k_msg_gather<0>, dim3((uint32_t)nt), dim3(msg_geom<0>::T), 0, st, rx, rx_len, pay_off,
-                               pay_len, keyrot, out_off, tile_first, meta, masked ? 1u : 0u, out, out_cap, t0);
+            hipLaunchKernelGGL((k_msg_gather<0, false>), dim3((uint32_t)nt), dim3(msg_geom<0>::T), 0, st, rx, rx_len,
+                               (const uint8_t*)nullptr, (uint64_t)0, pay_off, pay_len, keyrot, out_off, tile_first, meta,
+                               masked ? 1u : 0u, out, out_cap, t0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_msg_gather_joined(int g, const uint8_t* rx, uint64_t rx_len, const uint8_t* prev, uint64_t prev_len,
+                                    const msg_rows& rows, const uint64_t* out_off, const uint32_t* tile_first,
+                                    uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
+                                    hipStream_t st) {
+    const uint64_t per_launch = 0xFFFFFFFFull / 256;
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += per_launch) {
+        const uint64_t nt = ntiles - t0 < per_launch ? ntiles - t0 : per_launch;
+        if (g == 1)
+            hipLaunchKernelGGL((k_msg_gather<1, true>), dim3((uint32_t)nt), dim3(msg_geom<1>::T), 0, st, rx, rx_len, prev,
+                               prev_len, rows.src, rows.len, rows.key, out_off, tile_first, meta, masked ? 1u : 0u, out,
+                               out_cap, t0);
+        else
+            hipLaunchKernelGGL((k_msg_gather<0, true>), dim3((uint32_t)nt), dim3(msg_geom<0>::T), 0, st, rx, rx_len, prev,
+                               prev_len, rows.src, rows.len, rows.key, out_off, tile_first, meta, masked ? 1u : 0u, out,
+                               out_cap, t0);
     }
     return hipGetLastError();
 }
