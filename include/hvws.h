@@ -26,6 +26,9 @@
  *                (http/WebSocketParser.cpp:8-75) for a whole batch: the
  *                payload bytes with the headers squeezed out, unmasked on the
  *                way, and the table of the messages they form -- on the device.
+ *   hvws_messages_rfc  the same with RFC 6455's message rule in place of the
+ *                reference's: control frames apart from the fragmented data
+ *                message they interrupt, whole messages across batches.
  *   hvws_send_messages  WebSocketChannel::send (http/WebSocketChannel.cpp:5-48)
  *                for a batch of messages: one frame each, or fragmented into
  *                OPCODE, CONTINUE ..., CONTINUE + FIN, from a message table
@@ -625,6 +628,81 @@ int hvws_messages_joined(hvws_ctx* ctx, const uint8_t* d_rx, uint64_t rx_len, in
                          uint64_t out_cap, const hvws_msg_state* state_in, const uint8_t* d_prev, uint64_t prev_len,
                          const uint64_t* prev_off);
 int hvws_get_msg_carry(hvws_ctx* ctx, uint64_t* off);
+
+/* ---- RFC 6455 messages: control frames apart from fragmented messages ------ */
+/* hvws_messages_joined with the message rule of RFC 6455 sec. 5.4 in place of
+ * the reference's (quirk Q5 above): a control frame between the fragments of a
+ * data message is a message of its own and does not land in the data message.
+ * Text "AB" (not final), ping "PING", final continuation "CD" deliver
+ * (1, "ABCD") and (9, "PING").  For a server of its own on the batch interface;
+ * the drop-in, hvws_messages and hvws_messages_joined keep libhv's behaviour.
+ *
+ * The rule is the joined form's, applied to TWO VIRTUAL CONNECTIONS per
+ * connection.  Over segment s's frame records in frame-table order, with op =
+ * info & 0xF:
+ *   - data records: op < 8 and at least one of HVWS_I_HDR, HVWS_I_BODY,
+ *     HVWS_I_END set; they form virtual connection 2s;
+ *   - control records: op >= 8 with the same condition; they form 2s + 1;
+ *   - a record with none of the three bits (its header is still incomplete, it
+ *     has no payload bytes) belongs to neither.
+ * Each virtual connection follows hvws_messages_joined's contract exactly --
+ * its own carried span, latch, pieces, trailing open piece and HVWS_MSG_NOREC
+ * piece -- with two differences:
+ *   1. in the control class every record with HVWS_I_END closes a piece, with
+ *      or without FIN: a control frame is a message of its own;
+ *   2. a data piece with nothing latched reports opcode 0, not 8 (Q6 is not
+ *      reproduced: a lone final CONTINUE on a fresh connection selects no
+ *      reply).
+ * A new data header with a non-zero opcode while a data message is open
+ * overwrites the latch and appends, as in the other forms; failing such
+ * sequences, and every other protocol error, is not this call's.
+ *
+ * Output.  Connections are in order; connection s's part of d_out is its
+ * carried data bytes, the payload of its data records in stream order, its
+ * carried control bytes, the payload of its control records in stream order.
+ * Every HVWS_M_END piece is a whole message, contiguous in d_out, total ==
+ * len.  Pieces are ordered by connection, data pieces before control pieces;
+ * seg is the connection; rec is the frame-table index of the piece's last
+ * record and gives the stream order between the two classes (HVWS_MSG_NOREC
+ * for a piece of carried bytes only); HVWS_M_CTL marks control pieces.
+ * hvws_get_segment_messages gives each connection one first and one count over
+ * both classes.  The table may hold up to 2 * nseg pieces more than the batch
+ * has records.
+ *
+ * State.  One hvws_rfc_state per connection, in and out, all zero at accept.
+ * On the way in data_off / ctl_off point into d_prev and are ignored when the
+ * class's pending is 0; hvws_get_rfc_state (waits) returns the state on the
+ * way out, its offsets pointing into this call's d_out (0 when nothing is
+ * pending).  hvws_get_msg_state and hvws_get_msg_carry are HVWS_EINVAL after
+ * this call, hvws_get_rfc_state after the other two forms.
+ *
+ * The joined form's preconditions hold, each for both classes: HVWS_EINVAL
+ * with nothing written for a state no getter returns, a pending byte without
+ * d_prev, a carried range outside [0, prev_len), a misaligned d_out or d_prev,
+ * d_out overlapping the batch or d_prev; no read leaves the batch or d_prev; no
+ * byte at or beyond hvws_msg_bytes (all carried and payload bytes) is written;
+ * the records of a RUN step are built first; asynchronous on the ctx stream,
+ * reported by hvws_last_kernel_ms.  No wait when out_cap >= rx_len + all
+ * pending bytes of both classes (saturating); otherwise one wait, and
+ * HVWS_EINVAL with nothing written if the total does not fit.
+ *
+ * hvws_replies after this call: selection by opcode and policy is unchanged,
+ * but "close is final" goes by stream order.  With c the connection's selected
+ * CLOSE piece of the smallest rec, a piece produces a reply only if its rec <=
+ * rec(c), and of two pieces with that rec only c itself: a data message
+ * completing after the CLOSE frame is not echoed, a PING after it is not
+ * answered, a PING before it is.  Replies stay dense and in piece order, each
+ * connection's data replies before its control replies, so its CLOSE reply is
+ * the last frame of its byte range in the send's output.  HVWS_RF_DEFERRED is
+ * never set; closed_in works as for the other forms.   */
+typedef struct hvws_rfc_state {   /* 48 B per connection; all zero = fresh */
+    hvws_msg_state data, ctl;     /* the data class's and the control class's state */
+    uint64_t data_off, ctl_off;   /* where each class's pending bytes begin: in d_prev (in), in d_out (out) */
+} hvws_rfc_state;
+#define HVWS_M_CTL (1u << 6)      /* a piece of the control class (hvws_messages_rfc only) */
+int hvws_messages_rfc(hvws_ctx* ctx, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out,
+                      uint64_t out_cap, const hvws_rfc_state* state_in, const uint8_t* d_prev, uint64_t prev_len);
+int hvws_get_rfc_state(hvws_ctx* ctx, hvws_rfc_state* out);
 
 /* ---- batched send, device resident ---------------------------------------- */
 /* WebSocketChannel::send (http/WebSocketChannel.cpp:5-48) for n messages at

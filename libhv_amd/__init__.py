@@ -78,6 +78,10 @@ MSG_DTYPE = np.dtype(
 MSG_STATE_DTYPE = np.dtype([("pending", "<u8"), ("opcode", "<u4"), ("open", "<u4")])
 assert MSG_DTYPE.itemsize == 40 and MSG_STATE_DTYPE.itemsize == 16
 MSG_END, MSG_CONT = 1 << 4, 1 << 5
+# hvws_rfc_state and HVWS_M_CTL (hvws_messages_rfc)
+RFC_STATE_DTYPE = np.dtype([("data", MSG_STATE_DTYPE), ("ctl", MSG_STATE_DTYPE), ("data_off", "<u8"), ("ctl_off", "<u8")])
+assert RFC_STATE_DTYPE.itemsize == 48
+M_CTL = 1 << 6
 # hvws_tx_msg, HVWS_R_* and HVWS_RF_* (include/hvws.h)
 TX_MSG_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8"), ("flags", "<u4"), ("key", "<u4")])
 assert TX_MSG_DTYPE.itemsize == 24
@@ -178,6 +182,12 @@ _SIGS = {
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
     ),
     "hvws_get_msg_carry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_messages_rfc": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64],
+    ),
+    "hvws_get_rfc_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_msg_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "hvws_msg_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "hvws_get_messages": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
@@ -579,6 +589,27 @@ class Engine:
         of the trailing open piece: the connection's prev_off in its next batch."""
         out = np.zeros(max(nseg, 1), dtype=np.uint64)
         _check(lib().hvws_get_msg_carry(self.ctx, out.ctypes.data), "hvws_get_msg_carry")
+        return out[:nseg]
+
+    def messages_rfc(self, rx: DeviceBuffer, rx_len: int, masked: bool, out: DeviceBuffer, out_cap: int,
+                     state_in=None, prev=None, prev_len: int = 0) -> None:
+        """hvws_messages_rfc: messages_joined() with RFC 6455's message rule -- each
+        connection's control frames are messages of their own (M_CTL pieces, behind
+        the connection's data pieces) and no longer land in the fragmented data
+        message they interrupt.  state_in: one RFC_STATE_DTYPE entry per segment,
+        its offsets pointing into prev (None = all fresh)."""
+        st = None
+        if state_in is not None:
+            st = np.ascontiguousarray(state_in, dtype=RFC_STATE_DTYPE)
+        pp = prev.ptr if hasattr(prev, "ptr") else prev
+        _check(lib().hvws_messages_rfc(self.ctx, rx.ptr, rx_len, int(bool(masked)), out.ptr, out_cap,
+                                       st.ctypes.data if st is not None else None, pp, prev_len), "hvws_messages_rfc")
+
+    def rfc_state(self, nseg: int) -> np.ndarray:
+        """Per segment of the last messages_rfc() call, the state to carry into the
+        connection's next batch (RFC_STATE_DTYPE), offsets into that call's output."""
+        out = np.zeros(max(nseg, 1), dtype=RFC_STATE_DTYPE)
+        _check(lib().hvws_get_rfc_state(self.ctx, out.ctypes.data), "hvws_get_rfc_state")
         return out[:nseg]
 
     def message_table(self) -> np.ndarray:

@@ -264,6 +264,14 @@ struct hvws_ctx {
     // behind state_in in the same slot
     dbuf mj_len, mj_src, mj_key, mj_info, mj_prow, mj_carry;
     bool have_join = false;   // the last hvws_messages was the joined form
+    // hvws_messages_rfc: the class scan's scratch, each row's record, each
+    // virtual connection's carried row and record count; the states go up
+    // repacked (2 per connection, then their offsets) and come back as
+    // hvws_rfc_state in mg_out
+    dbuf mr_cls, mr_rec, mr_vbase, mr_vcnt;
+    std::vector<hvws_msg_state> rf_st;
+    std::vector<uint64_t> rf_off;
+    bool have_rfc = false;   // the last hvws_messages was the RFC form
     // hvws_send_messages: the message scan's scratch, each message's first
     // frame, {frames, bytes, bad, count, uniform layout}, and the per-frame rows
     // k_build reads (out_off and size in tx_off / tx_size)
@@ -2686,7 +2694,9 @@ uint64_t hvws_utf8_tile(void) { return U8_TILE; }
 static_assert(sizeof(dmsg) == sizeof(hvws_msg) && sizeof(dmsg) == 40, "dmsg mirrors hvws_msg");
 static_assert(sizeof(dmsg_state) == sizeof(hvws_msg_state) && sizeof(dmsg_state) == 16,
               "dmsg_state mirrors hvws_msg_state");
-static_assert(M_END == HVWS_M_END && M_CONT == HVWS_M_CONT, "piece bits");
+static_assert(M_END == HVWS_M_END && M_CONT == HVWS_M_CONT && M_CTL == HVWS_M_CTL, "piece bits");
+static_assert(sizeof(drfc_state) == sizeof(hvws_rfc_state) && sizeof(drfc_state) == 48,
+              "drfc_state mirrors hvws_rfc_state");
 
 // Message reassembly over the last scan's frame table (hvws_msg.hip): the
 // table pass, the tile index over the output, the gather -- all on the context
@@ -2694,7 +2704,9 @@ static_assert(M_END == HVWS_M_END && M_CONT == HVWS_M_CONT, "piece bits");
 // current table set only.  prev != nullptr: the joined form
 // (hvws_messages_joined), whose tables are over rows -- per segment its carried
 // span in prev->d, then its records -- and which may run with up to nseg pieces
-// more than records.
+// more than records.  rfc: the RFC form (hvws_messages_rfc), the joined form
+// over two virtual connections per connection -- vn states and offsets, 2s the
+// data class's and 2s + 1 the control class's.
 namespace {
 struct msg_prev {
     const uint8_t* d;
@@ -2703,7 +2715,7 @@ struct msg_prev {
 };
 
 int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
-                  const hvws_msg_state* state_in, const msg_prev* prev) {
+                  const hvws_msg_state* state_in, const msg_prev* prev, bool rfc = false) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_messages without a preceding hvws_scan");
@@ -2716,8 +2728,9 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         if (o < r + rx_len && r < o + out_cap) return set_err(HVWS_EINVAL, "hvws_messages: d_out overlaps the batch");
     }
     const uint32_t nseg = c->nseg;
+    const uint64_t vn = rfc ? 2ull * nseg : nseg;   // states: one per (virtual) connection
     if (state_in)
-        for (uint32_t s = 0; s < nseg; ++s)
+        for (uint64_t s = 0; s < vn; ++s)
             if ((state_in[s].open == 0 && state_in[s].pending != 0) || state_in[s].opcode > 15)
                 return set_err(HVWS_EINVAL, "hvws_messages: state_in is no state hvws_get_msg_state returns");
     // The joined form: every carried range inside prev, the output clear of it;
@@ -2727,7 +2740,7 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         if (((uintptr_t)prev->d & 15u) != 0)
             return set_err(HVWS_EINVAL, "hvws_messages_joined: d_prev must be 16-byte aligned");
         if (state_in)
-            for (uint32_t s = 0; s < nseg; ++s) {
+            for (uint64_t s = 0; s < vn; ++s) {
                 const uint64_t P = state_in[s].pending;
                 if (P == 0) continue;
                 if (!prev->d || !prev->off)
@@ -2745,7 +2758,7 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
     // c->nfr: the record count, or its bound while the count is on the device
     const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
-    const uint64_t ncap = rows ? cap + nseg : cap;   // rows, and the bound of the pieces
+    const uint64_t ncap = rows ? cap + vn : cap;   // rows, and the bound of the pieces
     // the output cannot exceed the batch and what is carried
     const uint64_t need = carried > UINT64_MAX - rx_len ? UINT64_MAX : rx_len + carried;
     const uint64_t bound = std::min(need, out_cap);
@@ -2759,8 +2772,8 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     HIP_OR(c->mg_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     // state_in, then (joined) prev_off
-    HIP_OR(c->mg_in.ensure((uint64_t)nseg * (sizeof(dmsg_state) + 8) + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_out.ensure((uint64_t)nseg * sizeof(dmsg_state) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_in.ensure(vn * (sizeof(dmsg_state) + 8) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg_out.ensure((uint64_t)nseg * (rfc ? sizeof(drfc_state) : sizeof(dmsg_state)) + 16), HVWS_ENOMEM);
     HIP_OR(c->mg_meta.ensure(64), HVWS_ENOMEM);
     if (rows) {
         HIP_OR(c->mj_len.ensure(ncap * 8 + 16), HVWS_ENOMEM);
@@ -2770,13 +2783,20 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         HIP_OR(c->mj_prow.ensure((ncap + 1) * 8), HVWS_ENOMEM);
         HIP_OR(c->mj_carry.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     }
+    if (rows && rfc) {
+        HIP_OR(c->mr_cls.ensure(msg_cls_bytes(cap)), HVWS_ENOMEM);
+        HIP_OR(c->mr_rec.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mr_vbase.ensure(vn * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mr_vcnt.ensure(vn * 8 + 16), HVWS_ENOMEM);
+    }
     c->have_msg = false;   // the tables are being rewritten
     c->have_join = false;
+    c->have_rfc = false;
     c->have_rep = false;   // ... which a reply table indexes
     const bool with_off = rows && carried;   // prev_off rides behind the states in the same slot
     if (state_in && nseg) {
-        const uint64_t sbytes = (uint64_t)nseg * sizeof(dmsg_state);
-        const uint64_t bytes = sbytes + (with_off ? (uint64_t)nseg * 8 : 0);
+        const uint64_t sbytes = vn * sizeof(dmsg_state);
+        const uint64_t bytes = sbytes + (with_off ? vn * 8 : 0);
         if (!c->mg_up_ev) HIP_OR(hipEventCreateWithFlags(&c->mg_up_ev, hipEventDisableTiming), HVWS_EHIP);
         if (c->mg_up_pending) {   // the previous pass's copy out of the slot
             HIP_OR(hipEventSynchronize(c->mg_up_ev), HVWS_EHIP);
@@ -2784,7 +2804,7 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         }
         HIP_OR(c->h_mg_in.ensure(bytes), HVWS_ENOMEM);
         memcpy(c->h_mg_in.p, state_in, sbytes);
-        if (with_off) memcpy((uint8_t*)c->h_mg_in.p + sbytes, prev->off, (uint64_t)nseg * 8);
+        if (with_off) memcpy((uint8_t*)c->h_mg_in.p + sbytes, prev->off, vn * 8);
         HIP_OR(hipMemcpyAsync(c->mg_in.p, c->h_mg_in.p, bytes, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
         HIP_OR(hipEventRecord(c->mg_up_ev, c->stream), HVWS_EHIP);
         c->mg_up_pending = true;
@@ -2796,15 +2816,25 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
         const dframes fr{nullptr, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), nullptr, nullptr,
                          c->T().f_keyrot.as<uint32_t>(), c->T().f_info.as<uint32_t>(), cap};
         const uint64_t* d_prev_off =
-            with_off ? reinterpret_cast<const uint64_t*>((uint8_t*)c->mg_in.p + (uint64_t)nseg * sizeof(dmsg_state))
-                     : nullptr;
-        HIP_OR(launch_msg_table_joined(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().counts.as<uint64_t>(),
-                                       c->T().bases.as<uint64_t>(), nseg,
-                                       state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p, mr,
-                                       c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(),
-                                       c->mg_count.as<uint64_t>(), c->mg_out.as<dmsg_state>(),
-                                       c->mj_carry.as<uint64_t>(), c->mg_meta.as<uint64_t>(), c->stream),
-               HVWS_EHIP);
+            with_off ? reinterpret_cast<const uint64_t*>((uint8_t*)c->mg_in.p + vn * sizeof(dmsg_state)) : nullptr;
+        if (rfc) {
+            const rfc_rows rr{c->mr_rec.as<uint64_t>(), c->mr_vbase.as<uint64_t>(), c->mr_vcnt.as<uint64_t>()};
+            HIP_OR(launch_msg_table_rfc(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().bases.as<uint64_t>(), nseg,
+                                        state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p,
+                                        c->mr_cls.p, mr, rr, c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(),
+                                        c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
+                                        c->mg_out.as<drfc_state>(), c->mg_meta.as<uint64_t>(), c->stream),
+                   HVWS_EHIP);
+        } else {
+            HIP_OR(launch_msg_table_joined(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().counts.as<uint64_t>(),
+                                           c->T().bases.as<uint64_t>(), nseg,
+                                           state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p,
+                                           mr, c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(),
+                                           c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
+                                           c->mg_out.as<dmsg_state>(), c->mj_carry.as<uint64_t>(),
+                                           c->mg_meta.as<uint64_t>(), c->stream),
+                   HVWS_EHIP);
+        }
     } else {
         HIP_OR(launch_msg_table(c->T().f_len.as<uint64_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(),
                                 cap, c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), nseg,
@@ -2854,7 +2884,8 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     if ((rc = free_event()) != HVWS_OK) return rc;
     if (!fits) return set_err(HVWS_EINVAL, "hvws_messages: the payload does not fit out_cap");
     c->have_msg = true;
-    c->have_join = prev != nullptr;
+    c->have_join = prev != nullptr && !rfc;
+    c->have_rfc = rfc;
     c->mg_nseg = nseg;
     c->mg_cap = ncap;
     return HVWS_OK;
@@ -2871,6 +2902,38 @@ int hvws_messages_joined(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int 
                          const uint64_t* prev_off) {
     const msg_prev prev{d_prev, d_prev ? prev_len : 0, prev_off};
     return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in, &prev);
+}
+
+// The RFC form: the states repacked per virtual connection (2s data, 2s + 1
+// control), their offsets into d_prev behind them, then the joined pass.
+int hvws_messages_rfc(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, uint8_t* d_out, uint64_t out_cap,
+                      const hvws_rfc_state* state_in, const uint8_t* d_prev, uint64_t prev_len) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    const uint32_t nseg = c->nseg;
+    if (state_in) {
+        c->rf_st.resize(2ull * nseg);
+        c->rf_off.resize(2ull * nseg);
+        for (uint32_t s = 0; s < nseg; ++s) {
+            c->rf_st[2ull * s] = state_in[s].data;
+            c->rf_st[2ull * s + 1] = state_in[s].ctl;
+            c->rf_off[2ull * s] = state_in[s].data_off;
+            c->rf_off[2ull * s + 1] = state_in[s].ctl_off;
+        }
+    }
+    const msg_prev prev{d_prev, d_prev ? prev_len : 0, state_in ? c->rf_off.data() : nullptr};
+    return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in ? c->rf_st.data() : nullptr, &prev, true);
+}
+
+int hvws_get_rfc_state(hvws_ctx* c, hvws_rfc_state* out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg || !c->have_rfc) return set_err(HVWS_EINVAL, "no hvws_messages_rfc call yet");
+    const uint64_t nseg = c->mg_nseg;
+    if (out && nseg)
+        HIP_OR(hipMemcpyAsync(out, c->mg_out.p, nseg * sizeof(drfc_state), hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
 }
 
 int hvws_get_msg_carry(hvws_ctx* c, uint64_t* off) {
@@ -2934,6 +2997,7 @@ int hvws_get_msg_state(hvws_ctx* c, hvws_msg_state* out) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    if (c->have_rfc) return set_err(HVWS_EINVAL, "hvws_get_msg_state after hvws_messages_rfc: hvws_get_rfc_state");
     const uint64_t nseg = c->mg_nseg;
     if (out && nseg)
         HIP_OR(hipMemcpyAsync(out, c->mg_out.p, nseg * sizeof(dmsg_state), hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
@@ -3529,7 +3593,7 @@ int hvws_replies(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
                           c->mg_count.as<uint64_t>(), nseg, policy, closed_in ? c->rp_closed.as<uint8_t>() : nullptr,
                           c->rp_limit.as<uint64_t>(), c->rp_scan.as<uint64_t>(), c->rp_msgs.as<dtxmsg>(),
                           c->rp_piece.as<uint64_t>(), c->rp_first.as<uint64_t>(), c->rp_count.as<uint64_t>(),
-                          c->rp_flags.as<uint8_t>(), c->stream),
+                          c->rp_flags.as<uint8_t>(), c->have_rfc, c->stream),
            HVWS_EHIP);
     c->have_rep = true;
     c->rp_nseg = nseg;

@@ -500,7 +500,11 @@ struct dmsg {
     uint64_t off, len, total, rec;
     uint32_t seg, info;
 };
-enum : uint32_t { M_END = 1u << 4, M_CONT = 1u << 5 };
+struct drfc_state {   // mirrors hvws_rfc_state
+    dmsg_state data, ctl;
+    uint64_t data_off, ctl_off;
+};
+enum : uint32_t { M_END = 1u << 4, M_CONT = 1u << 5, M_CTL = 1u << 6 };
 constexpr uint64_t MSG_TILE = 16384;   // output bytes of k_msg_gather's largest tile (every geometry's divides it)
 // k_msg_gather geometry for a batch of rx_len bytes in at most cap records
 // ($HVWS_EXPERIMENT msg, else by the mean bytes per record) and its tile
@@ -551,6 +555,28 @@ hipError_t launch_msg_gather_joined(int g, const uint8_t* rx, uint64_t rx_len, c
                                     const msg_rows& rows, const uint64_t* out_off, const uint32_t* tile_first,
                                     uint64_t ntiles, const uint64_t* meta, int masked, uint8_t* out, uint64_t out_cap,
                                     hipStream_t st);
+// The RFC form (hvws_messages_rfc): rows as in the joined form, scattered into
+// output order -- per connection its data carried row and data records, then
+// its control carried row and control records: cap + 2 nseg of them, two
+// virtual connections per connection.  rec: each row's frame-table index;
+// vbase / vcnt: each virtual connection's carried row and record count
+// (2 nseg words each).
+struct rfc_rows {
+    uint64_t* rec;
+    uint64_t* vbase;
+    uint64_t* vcnt;
+};
+uint64_t msg_cls_bytes(uint64_t cap);
+// launch_msg_table_joined over those rows.  scratch: msg_scratch_bytes(cap +
+// 2 nseg); cls_scratch: msg_cls_bytes(cap); row tables and out_off: cap + 2 nseg
+// entries; msgs: one more; vstate_in / voff (device, 2 nseg entries: 2s data,
+// 2s + 1 control) may be null when nothing is pending; state_out: nseg entries.
+// launch_msg_gather_joined and the tile index then run over rows unchanged.
+hipError_t launch_msg_table_rfc(const dframes& fr, int masked, const uint64_t* nfr_dev, uint64_t cap,
+                                const uint64_t* bases, uint32_t nseg, const dmsg_state* vstate_in,
+                                const uint64_t* voff, void* scratch, void* cls_scratch, const msg_rows& rows,
+                                const rfc_rows& rr, uint64_t* out_off, dmsg* msgs, uint64_t* seg_first,
+                                uint64_t* seg_count, drfc_state* state_out, uint64_t* meta, hipStream_t st);
 // Batched send and server replies (hvws_send.hip; include/hvws.h has both
 // contracts).  dtxmsg mirrors hvws_tx_msg.
 struct dtxmsg {
@@ -576,12 +602,13 @@ hipError_t launch_send_expand(const dtxmsg* msgs, const void* scratch, const uin
 // The reply rule over hvws_messages' piece table (msgs, mg_meta[2] pieces
 // clamped to cap, per-segment seg_first / seg_count).  closed_in: device, nseg
 // bytes or null; limit: nseg words; scratch: rep_scratch_words(cap) words, of
-// which word `cap` receives the reply count; out / piece: cap entries.
+// which word `cap` receives the reply count; out / piece: cap entries.  by_rec:
+// the table is hvws_messages_rfc's, "close is final" goes by the pieces' rec.
 uint64_t rep_scratch_words(uint64_t cap);
 hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t cap, const uint64_t* seg_first,
                           const uint64_t* seg_count, uint32_t nseg, uint32_t policy, const uint8_t* closed_in,
                           uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
-                          uint64_t* rep_count, uint8_t* flags, hipStream_t st);
+                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st);
 // Predicted frames above which a uniform segment is verified grid-wide (k_verify).
 uint64_t spec_min();
 uint64_t set_spec_min(uint64_t v);   // 0 = default; returns the previous value

@@ -43,6 +43,13 @@
 // source with a buffer selector, key, info with the piece-closing bit); the
 // scan, the three table kernels, the tile index and the gather then take rows
 // where the plain form takes records, and the work stays spread by rows.
+//
+// The RFC form (hvws_messages_rfc) is the joined form over two virtual
+// connections per connection, the data records and the control records: one
+// more scan ranks every record within its class, k_rfc_rows scatters the rows
+// into output order (per connection: data carried row, data records, control
+// carried row, control records), and everything from the scan on runs over
+// those rows as it does over the joined form's.
 #include <stdlib.h>
 
 #include "hvws_dev.h"
@@ -79,6 +86,7 @@ struct msg_load {
     const uint64_t* bases;
     uint32_t nseg;
     static constexpr bool JOINED = false;
+    static constexpr bool RFC = false;
     __device__ __forceinline__ uint64_t nrec() const { return *nfr_p < cap ? *nfr_p : cap; }
     __device__ __forceinline__ static bool fin_end(uint32_t inf) { return (inf & I_END) && (inf & F_FIN); }
     __device__ __forceinline__ uint64_t len(uint64_t r) const { return pay_len[r]; }
@@ -113,6 +121,7 @@ struct row_load {
     const uint64_t* bases;
     uint32_t nseg;
     static constexpr bool JOINED = true;
+    static constexpr bool RFC = false;
     __device__ __forceinline__ uint64_t records() const { return *nfr_p < cap ? *nfr_p : cap; }
     __device__ __forceinline__ uint64_t nrec() const { return records() + nseg; }
     __device__ __forceinline__ static bool fin_end(uint32_t inf) { return (inf & I_END) && (inf & F_FIN); }
@@ -176,6 +185,158 @@ __global__ __launch_bounds__(256) void k_join_rows(row_load in, const uint64_t* 
     }
 }
 
+// ---- the RFC form's rows (hvws_messages_rfc)
+// Two virtual connections per connection: 2s takes the data records (opcode
+// below 8), 2s + 1 the control records, each behind a carried row of its own.
+// Connection s's rows begin at R(s) = min(bases[s], records) + 2s and lie in
+// output order: the data carried row, the data records, the control carried
+// row, the control records, then the records of neither class (a header still
+// incomplete: no bytes, no latch, never a piece's last row), which ride at the
+// end of 2s + 1 so that the batch has records + 2 nseg rows whatever it holds.
+struct cls2 {
+    uint64_t ctl, none;   // control records, records of neither class
+};
+__device__ __forceinline__ cls2 scan_op(const cls2& a, const cls2& b) { return cls2{a.ctl + b.ctl, a.none + b.none}; }
+
+// 0: a data record, 1: a control record, 2: neither
+__device__ __forceinline__ uint32_t rfc_class(uint32_t inf) {
+    if (!(inf & (I_HDR | I_BODY | I_END))) return 2u;
+    return (inf & F_OPMASK) >= 8u ? 1u : 0u;
+}
+
+struct cls_load {
+    const uint32_t* info;
+    const uint64_t* nfr_p;
+    uint64_t cap;
+    __device__ __forceinline__ cls2 operator()(uint64_t r) const {
+        if (r >= (*nfr_p < cap ? *nfr_p : cap)) return cls2{};
+        const uint32_t k = rfc_class(info[r]);
+        return cls2{k == 1u ? 1u : 0u, k == 2u ? 1u : 0u};
+    }
+};
+
+// The class scan's result for record r (block-relative values and block bases,
+// as msg_scan below); records at or beyond cap read the total.
+struct cls_scan {
+    const cls2* ex;
+    const cls2* base;   // nullptr: one block
+    const cls2* total;
+    uint64_t cap;
+    __device__ __forceinline__ cls2 operator()(uint64_t r) const {
+        if (r >= cap) return *total;
+        const cls2 v = ex[r];
+        return base ? scan_op(base[r / SCAN_B], v) : v;
+    }
+};
+
+// row_load over the scattered rows.  nseg counts VIRTUAL connections; vbase[v]
+// is v's carried row (strictly increasing) and row_rec a row's frame-table
+// index.  A control frame is a message of its own: its END closes a piece with
+// or without FIN (opcodes 8 .. 15 have bit 3).
+struct rfc_load {
+    const uint64_t* row_len;
+    const uint32_t* row_info;
+    const uint64_t* nfr_p;
+    uint64_t cap;   // records
+    const uint64_t* vbase;
+    const uint64_t* row_rec;
+    uint32_t nseg;
+    static constexpr bool JOINED = true;
+    static constexpr bool RFC = true;
+    __device__ __forceinline__ uint64_t records() const { return *nfr_p < cap ? *nfr_p : cap; }
+    __device__ __forceinline__ uint64_t nrec() const { return records() + nseg; }
+    __device__ __forceinline__ static bool fin_end(uint32_t inf) { return (inf & I_END) && (inf & (F_FIN | 8u)); }
+    __device__ __forceinline__ uint64_t len(uint64_t i) const { return row_len[i]; }
+    __device__ __forceinline__ uint32_t inf(uint64_t i) const { return row_info[i]; }
+    __device__ __forceinline__ uint64_t base(uint32_t v) const { return vbase[v]; }
+    __device__ __forceinline__ uint64_t rec_of(uint64_t i) const { return row_rec[i]; }
+    __device__ __forceinline__ uint32_t seg_of(uint64_t i) const {   // nseg > 0: row 0 is virtual connection 0's
+        uint32_t lo = 0, hi = nseg;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (vbase[mid] > i) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo - 1u;
+    }
+    __device__ __forceinline__ msg3 operator()(uint64_t i) const {
+        if (i >= nrec()) return msg3{};
+        const uint32_t inf = row_info[i];
+        const uint64_t latch = (inf & I_HDR) && (inf & F_OPMASK) ? i + 1 : 0;
+        return msg3{row_len[i], inf & ROW_CLOSE ? 1u : 0u, latch};
+    }
+};
+
+// The row table of the RFC form, one thread per row slot: slot R(s) writes
+// connection s's data carried row (and vbase / vcnt of both virtual
+// connections), slot R(s) + 1 its control carried row, slot R(s) + 2 + k the
+// row of the connection's k-th record, each at its place in output order: the
+// stable partition comes from cls, the exclusive scan of cls_load.  A carried
+// row closes a piece only when its class has no records and bytes are pending;
+// a record's row when its frame completes a message of its class or when it is
+// its class's last in the connection.
+__global__ __launch_bounds__(256) void k_rfc_rows(const uint64_t* __restrict__ nfr_p, uint64_t cap,
+                                                  const uint64_t* __restrict__ bases, uint32_t nseg, cls_scan cls,
+                                                  const uint64_t* __restrict__ pay_off,
+                                                  const uint64_t* __restrict__ pay_len,
+                                                  const uint32_t* __restrict__ info,
+                                                  const uint32_t* __restrict__ keyrot, uint32_t masked,
+                                                  const dmsg_state* __restrict__ vstate_in,
+                                                  const uint64_t* __restrict__ voff, uint64_t* __restrict__ row_len,
+                                                  uint64_t* __restrict__ row_src, uint32_t* __restrict__ row_key,
+                                                  uint32_t* __restrict__ row_info, uint64_t* __restrict__ row_rec,
+                                                  uint64_t* __restrict__ vbase, uint64_t* __restrict__ vcnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t n = *nfr_p < cap ? *nfr_p : cap;
+    if (i >= n + 2ull * nseg) return;
+    auto rbase = [&](uint32_t s) { return bases[s] < n ? bases[s] : n; };
+    uint32_t lo = 0, hi = nseg;   // the last connection with R(s) <= i (R(0) = 0)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rbase(mid) + 2ull * mid > i) hi = mid;
+        else lo = mid + 1;
+    }
+    const uint32_t s = lo - 1u;
+    const uint64_t rb = rbase(s), re = s + 1 < nseg ? rbase(s + 1) : n;
+    const cls2 c0 = cls(rb), c1 = cls(re);
+    const uint64_t nc = c1.ctl - c0.ctl, nn = c1.none - c0.none, nd = re - rb - nc - nn;
+    const uint64_t R = rb + 2ull * s, j = i - R;
+    if (j < 2) {   // a carried row
+        const uint32_t v = 2u * s + (uint32_t)j;
+        const uint64_t at_row = j ? R + 1 + nd : R, mine = j ? nc : nd;
+        const uint64_t P = vstate_in ? vstate_in[v].pending : 0;
+        row_len[at_row] = P;
+        row_src[at_row] = P ? ROW_PREV | voff[v] : 0;
+        row_key[at_row] = 0;
+        row_info[at_row] = mine == 0 && P ? ROW_CLOSE : 0u;
+        row_rec[at_row] = ~0ull;
+        vbase[v] = at_row;
+        vcnt[v] = mine;
+        return;
+    }
+    const uint64_t r = rb + j - 2;
+    const uint32_t inf = info[r];
+    const uint32_t k = rfc_class(inf);
+    const cls2 c = cls(r);
+    const uint64_t kc = c.ctl - c0.ctl, kn = c.none - c0.none, kd = r - rb - kc - kn;
+    if (k == 2u) {
+        const uint64_t d = R + 2 + nd + nc + kn;
+        row_len[d] = 0;
+        row_src[d] = 0;
+        row_key[d] = 0;
+        row_info[d] = 0;
+        row_rec[d] = r;
+        return;
+    }
+    const uint64_t d = k ? R + 2 + nd + kc : R + 1 + kd;
+    const bool last = k ? kc + 1 == nc : kd + 1 == nd;
+    row_len[d] = pay_len[r];
+    row_src[d] = pay_off[r];
+    row_key[d] = masked ? keyrot[r] : 0u;
+    row_info[d] = inf | (rfc_load::fin_end(inf) || last ? ROW_CLOSE : 0u);
+    row_rec[d] = r;
+}
+
 // The scan's result for record r: its block-relative value and its block's base.
 struct msg_scan {
     const msg3* ex;
@@ -233,11 +394,16 @@ __global__ __launch_bounds__(256) void k_msg_pieces(LOAD in, msg_scan sc, const 
     const uint32_t inf = in.inf(r);
     const msg3 own = in(r);
     const uint64_t latch = e.latch > own.latch ? e.latch : own.latch;
-    const uint32_t op = latch > b ? in.inf(latch - 1) & F_OPMASK : (st.opcode ? st.opcode : 8u);
+    uint32_t none = 8u;   // nothing latched (Q6)
+    if constexpr (LOAD::RFC) none = seg & 1u ? 8u : 0u;   // ... which the RFC form's data class does not reproduce
+    const uint32_t op = latch > b ? in.inf(latch - 1) & F_OPMASK : (st.opcode ? st.opcode : none);
     dmsg m;
     m.off = off;
     m.len = e.bytes + own.bytes - off;   // joined: the first piece's rows begin with the carried one
-    if constexpr (LOAD::JOINED) {
+    if constexpr (LOAD::RFC) {
+        m.total = m.len;
+        m.rec = in.rec_of(r);   // ~0 for a carried row
+    } else if constexpr (LOAD::JOINED) {
         m.total = m.len;
         m.rec = r == b ? ~0ull : r - seg - 1;   // a carried row closes the piece without a record
     } else {
@@ -246,6 +412,10 @@ __global__ __launch_bounds__(256) void k_msg_pieces(LOAD in, msg_scan sc, const 
     }
     m.seg = seg;
     m.info = op | (LOAD::fin_end(inf) ? M_END : 0u) | (first && st.open ? M_CONT : 0u);
+    if constexpr (LOAD::RFC) {   // seg counts virtual connections
+        m.seg = seg >> 1;
+        m.info |= seg & 1u ? M_CTL : 0u;
+    }
     msgs[p] = m;
 }
 
@@ -329,6 +499,58 @@ __global__ __launch_bounds__(256) void k_join_segs(row_load in, msg_scan sc, con
     }
     state_out[s] = o;
     carry_off[s] = off;
+}
+
+// k_join_segs over the two virtual connections of each connection: first /
+// count cover both classes (data pieces, then control pieces); state_out is
+// hvws_rfc_state, each class's offset being where its trailing open piece
+// begins in the output (0 when nothing is pending).
+__global__ __launch_bounds__(256) void k_rfc_segs(rfc_load in, msg_scan sc, const uint64_t* __restrict__ vcnt,
+                                                  const dmsg_state* __restrict__ vstate_in,
+                                                  const dmsg* __restrict__ msgs, uint64_t* __restrict__ seg_first,
+                                                  uint64_t* __restrict__ seg_count, drfc_state* __restrict__ state_out) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (2u * s >= in.nseg) return;
+    drfc_state out;
+    uint64_t pieces = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 2; ++j) {
+        const uint32_t v = 2u * s + j;
+        const uint64_t b = in.base(v), cnt = vcnt[v];
+        dmsg_state st = dmsg_state{0, 0, 0};
+        if (vstate_in) st = vstate_in[v];
+        const uint64_t first = sc(b).close;
+        if (j == 0) seg_first[s] = first;
+        dmsg_state o = st;
+        uint64_t off = 0;
+        if (cnt == 0) {   // no records: the state unchanged; carried bytes are one open piece
+            pieces += st.pending ? 1 : 0;
+            if (st.pending) off = msgs[first].off;
+        } else {
+            const uint64_t last = b + cnt;
+            const msg3 e = sc(last), own = in(last);
+            pieces += e.close + 1 - first;   // the class's last row closes a piece
+            const uint64_t latch = e.latch > own.latch ? e.latch : own.latch;
+            o.opcode = latch > b ? in.inf(latch - 1) & F_OPMASK : st.opcode;
+            if (rfc_load::fin_end(in.inf(last))) {
+                o.open = 0;
+                o.pending = 0;
+            } else {
+                o.open = 1;
+                o.pending = msgs[e.close].total;
+                if (o.pending) off = msgs[e.close].off;
+            }
+        }
+        if (j == 0) {
+            out.data = o;
+            out.data_off = off;
+        } else {
+            out.ctl = o;
+            out.ctl_off = off;
+        }
+    }
+    seg_count[s] = pieces;
+    state_out[s] = out;
 }
 
 // ------------------------------------------------------------ k_msg_gather
@@ -648,6 +870,42 @@ hipError_t launch_msg_table_joined(const dframes& fr, int masked, const uint64_t
     hipLaunchKernelGGL(k_msg_pieces<row_load>, dim3(rb), dim3(256), 0, st, in, sc, total, state_in, rows.prow, msgs);
     hipLaunchKernelGGL(k_join_segs, dim3((nseg + 255) / 256), dim3(256), 0, st, in, sc, counts, state_in, msgs,
                        seg_first, seg_count, state_out, carry_off);
+    return hipGetLastError();
+}
+
+uint64_t msg_cls_bytes(uint64_t cap) { return (cap + 16 + scan_tmp_words(cap)) * sizeof(cls2); }
+
+hipError_t launch_msg_table_rfc(const dframes& fr, int masked, const uint64_t* nfr_dev, uint64_t cap,
+                                const uint64_t* bases, uint32_t nseg, const dmsg_state* vstate_in,
+                                const uint64_t* voff, void* scratch, void* cls_scratch, const msg_rows& rows,
+                                const rfc_rows& rr, uint64_t* out_off, dmsg* msgs, uint64_t* seg_first,
+                                uint64_t* seg_count, drfc_state* state_out, uint64_t* meta, hipStream_t st) {
+    if (nseg == 0) return hipErrorInvalidValue;   // row 0 is connection 0's
+    const uint64_t nrows = cap + 2ull * nseg;
+    cls2* cls = reinterpret_cast<cls2*>(cls_scratch);
+    cls2* cls_total = cls + cap;   // one value; 16 are set aside
+    cls2* cls_tmp = cls + cap + 16;
+    hipError_t e = launch_scan_of(cls_load{fr.info, nfr_dev, cap}, cls, cap, cls_tmp, cls_total, st, false);
+    if (e != hipSuccess) return e;
+    const uint64_t cb = (cap + SCAN_B - 1) / SCAN_B;
+    const cls_scan cs{cls, cb > 1 ? cls_tmp + cb : (const cls2*)nullptr, cls_total, cap};
+    msg3* ex = reinterpret_cast<msg3*>(scratch);
+    msg3* total = ex + nrows;
+    msg3* tmp = ex + nrows + 16;
+    const uint32_t rb = (uint32_t)((nrows + 255) / 256);
+    hipLaunchKernelGGL(k_rfc_rows, dim3(rb), dim3(256), 0, st, nfr_dev, cap, bases, nseg, cs, fr.pay_off,
+                       fr.pay_len, fr.info, fr.keyrot, masked ? 1u : 0u, vstate_in, voff, rows.len, rows.src, rows.key,
+                       rows.info, rr.rec, rr.vbase, rr.vcnt);
+    const rfc_load in{rows.len, rows.info, nfr_dev, cap, rr.vbase, rr.rec, 2u * nseg};
+    e = launch_scan_of(in, ex, nrows, tmp, total, st, false);
+    if (e != hipSuccess) return e;
+    const uint64_t nb = (nrows + SCAN_B - 1) / SCAN_B;
+    const msg_scan sc{ex, nb > 1 ? tmp + nb : (const msg3*)nullptr};
+    hipLaunchKernelGGL(k_msg_records<rfc_load>, dim3(rb), dim3(256), 0, st, in, sc, total, out_off, msgs, rows.prow,
+                       meta);
+    hipLaunchKernelGGL(k_msg_pieces<rfc_load>, dim3(rb), dim3(256), 0, st, in, sc, total, vstate_in, rows.prow, msgs);
+    hipLaunchKernelGGL(k_rfc_segs, dim3((nseg + 255) / 256), dim3(256), 0, st, in, sc, rr.vcnt, vstate_in, msgs,
+                       seg_first, seg_count, state_out);
     return hipGetLastError();
 }
 

@@ -179,7 +179,11 @@ __device__ __forceinline__ uint32_t reply_op(uint32_t info, uint32_t policy) {
     return 0;
 }
 
-// limit[s]: pieces of segment s at or beyond it send nothing (~0: no limit)
+// limit[s]: pieces of segment s at or beyond it send nothing (~0: no limit).
+// by_rec (after hvws_messages_rfc, whose pieces are not in stream order: data
+// pieces before control pieces): the limit is 1 + the rec of the selected CLOSE
+// piece with the smallest rec, and a piece sends when its rec lies below that
+// record or when it is that CLOSE itself.
 __global__ __launch_bounds__(256) void k_rep_init(const uint8_t* __restrict__ closed_in, uint32_t nseg,
                                                   unsigned long long* __restrict__ limit) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,12 +193,13 @@ __global__ __launch_bounds__(256) void k_rep_init(const uint8_t* __restrict__ cl
 __device__ __forceinline__ uint64_t rep_pieces(const uint64_t* meta, uint64_t cap) { return meta[2] < cap ? meta[2] : cap; }
 
 __global__ __launch_bounds__(256) void k_rep_close(const dmsg* __restrict__ msgs, const uint64_t* __restrict__ mg_meta,
-                                                   uint64_t cap, uint32_t policy,
+                                                   uint64_t cap, uint32_t policy, uint32_t by_rec,
                                                    unsigned long long* __restrict__ limit) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= rep_pieces(mg_meta, cap)) return;
     const dmsg m = msgs[p];
-    if (reply_op(m.info, policy) == 8) atomicMin(&limit[m.seg], (unsigned long long)(p + 1));
+    // an END piece has a record: rec + 1 does not wrap
+    if (reply_op(m.info, policy) == 8) atomicMin(&limit[m.seg], (unsigned long long)((by_rec ? m.rec : p) + 1));
 }
 
 // 1 for a piece that is answered on the device
@@ -204,10 +209,15 @@ struct rep_load {
     uint64_t cap;
     uint32_t policy;
     const unsigned long long* limit;
+    uint32_t by_rec;
     __device__ __forceinline__ uint64_t operator()(uint64_t p) const {
         if (p >= rep_pieces(mg_meta, cap)) return 0;
         const dmsg m = msgs[p];
-        return reply_op(m.info, policy) && p < limit[m.seg] && m.total == m.len ? 1u : 0u;
+        const uint32_t op = reply_op(m.info, policy);
+        if (!op || m.total != m.len) return 0;
+        const unsigned long long lim = limit[m.seg];
+        if (by_rec) return m.rec + 1 < lim || (m.rec + 1 == lim && op == 8) ? 1u : 0u;
+        return p < lim ? 1u : 0u;
     }
 };
 
@@ -238,7 +248,7 @@ __global__ __launch_bounds__(256) void k_rep_segs(rep_load in, const uint64_t* _
     rep_count[s] = b - a;
     const unsigned long long lim = in.limit[s];
     uint32_t fl = lim != ~0ull ? RF_CLOSED : 0u;
-    if (cnt && lim > p0) {   // only a segment's first piece can complete an earlier batch's message
+    if (cnt && lim > p0 && !in.by_rec) {   // only a segment's first piece can complete an earlier batch's message
         const dmsg m = in.msgs[p0];
         if (reply_op(m.info, in.policy) && m.total != m.len) fl |= RF_DEFERRED;
     }
@@ -279,17 +289,18 @@ uint64_t rep_scratch_words(uint64_t cap) { return cap + 16 + scan_tmp_words(cap)
 hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t cap, const uint64_t* seg_first,
                           const uint64_t* seg_count, uint32_t nseg, uint32_t policy, const uint8_t* closed_in,
                           uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
-                          uint64_t* rep_count, uint8_t* flags, hipStream_t st) {
+                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st) {
     unsigned long long* lim = reinterpret_cast<unsigned long long*>(limit);
     uint64_t* ex = scratch;
     uint64_t* total = ex + cap;   // the reply count: the send's d_n
     uint64_t* tmp = ex + cap + 16;
     const uint32_t sb = (nseg + 255) / 256, pb = (uint32_t)((cap + 255) / 256);
     if (sb) hipLaunchKernelGGL(k_rep_init, dim3(sb), dim3(256), 0, st, closed_in, nseg, lim);
-    if (pb) hipLaunchKernelGGL(k_rep_close, dim3(pb), dim3(256), 0, st, msgs, mg_meta, cap, policy, lim);
+    if (pb) hipLaunchKernelGGL(k_rep_close, dim3(pb), dim3(256), 0, st, msgs, mg_meta, cap, policy, by_rec ? 1u : 0u,
+                               lim);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const rep_load in{msgs, mg_meta, cap, policy, lim};
+    const rep_load in{msgs, mg_meta, cap, policy, lim, by_rec ? 1u : 0u};
     e = launch_scan_of(in, ex, cap, tmp, total, st);
     if (e != hipSuccess) return e;
     if (pb) hipLaunchKernelGGL(k_rep_scatter, dim3(pb), dim3(256), 0, st, in, ex, out, piece);
