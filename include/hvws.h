@@ -38,6 +38,9 @@
  *                PING, a CLOSE for the first CLOSE and nothing after it,
  *                optionally an echo of data messages -- as a message table
  *                hvws_send_messages sends without a host read in between.
+ *   hvws_check   what the reference leaves out altogether: failing a connection
+ *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
+ *                record and close code per connection, on the device; opt-in.
  *   hvws_wsp_*   C handle over the WebSocketParser class
  *                (http/WebSocketParser.h:19-31) for FFI callers.
  *
@@ -346,8 +349,9 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
  * (tile index, source spans, k_build), or of the last hvws_utf8 (its tile
  * index and all three kernels), or of the last hvws_messages (table pass,
  * tile index and gather), or of the last hvws_send_messages' device work after
- * its wait (expansion, tile index, spans, k_build) -- whichever was called
- * last; the default build geometry's name. */
+ * its wait (expansion, tile index, spans, k_build), or of the last hvws_check
+ * (its scan and table kernels) -- whichever was called last; the default build
+ * geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
 const char* hvws_build_kernel_name(void);
 /* The k_build geometry the last hvws_build_frames on ctx ran: one-wave
@@ -442,7 +446,7 @@ uint32_t hvws_set_validation(hvws_ctx* ctx, uint32_t classes);
  * the batches cut the stream.  A state word carried in with REJECT (or with
  * 8..14, which are no states) gives bad[s] = the segment's first record index
  * (even when the segment has no records) and carries out REJECT.  A Close
- * frame's reason text is not checked.
+ * frame's reason text is not checked (hvws_check's HVWS_C_CLOSE_UTF8 does).
  *
  * An event loop keeps one uint32_t per connection next to its
  * websocket_parser carry: 0 at accept, state_in[s] on the way in, state_out[s]
@@ -655,7 +659,8 @@ int hvws_get_msg_carry(hvws_ctx* ctx, uint64_t* off);
  *      reply).
  * A new data header with a non-zero opcode while a data message is open
  * overwrites the latch and appends, as in the other forms; failing such
- * sequences, and every other protocol error, is not this call's.
+ * sequences, and every other protocol error, is not this call's (hvws_check,
+ * below, does it).
  *
  * Output.  Connections are in order; connection s's part of d_out is its
  * carried data bytes, the payload of its data records in stream order, its
@@ -817,6 +822,105 @@ int64_t hvws_reply_count(hvws_ctx* ctx);
 int hvws_get_replies(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* piece, uint64_t first, uint64_t n);
 int hvws_get_segment_replies(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
 int hvws_get_reply_flags(hvws_ctx* ctx, uint8_t* out);
+
+/* ---- failing a connection, device resident (RFC 6455 sec. 7.1.7) ---------- */
+/* Which connections of a batch broke the protocol, at which record and with
+ * which close code -- joined on the device from the tables the earlier passes
+ * left there, so a server on the batch interface need not read the frame
+ * table, the piece table and the UTF-8 verdicts back and walk them per
+ * connection before it may send.  The reference fails nothing; like
+ * hvws_set_validation and hvws_utf8 this is behaviour a caller opts into.
+ *
+ * hvws_check runs after hvws_messages_rfc on ctx: HVWS_EINVAL after no message
+ * call, after hvws_messages or hvws_messages_joined, or when a scan has run on
+ * ctx since that hvws_messages_rfc.  It is asynchronous on the ctx stream, does
+ * not wait and writes nothing another pass reads; hvws_last_kernel_ms reports
+ * it when it was the last call.  The message call's d_out must still hold that
+ * call's bytes: the pass reads the Close bodies there.
+ *
+ * State.  One uint32_t per connection beside its hvws_rfc_state: 0 at accept,
+ * state_in[s] on the way in (host, nseg words, NULL = all 0), hvws_get_check's
+ * state_out[s] on the way out.  HVWS_CK_OPEN: a data message is open;
+ * HVWS_CK_FAILED: the connection has failed (sticky).  Any other bit in
+ * state_in is HVWS_EINVAL.  A word carried in with HVWS_CK_FAILED gives
+ * fail_rec[s] = the connection's first record index (even when it has no
+ * records, as hvws_utf8 does it), why[s] = 0 and code[s] = 0 -- the batch that
+ * failed it reported them -- and carries out HVWS_CK_FAILED alone.
+ *
+ * Classes (bits of `classes`; any other bit: HVWS_EINVAL), where each finds
+ * its violation, and the close code it stands for:
+ *   HVWS_C_HEADER      a record with HVWS_I_INVALID (the hvws_set_validation
+ *                      classes in force when it was scanned): that record, 1002;
+ *   HVWS_C_SEQUENCE    sec. 5.4: a record with HVWS_I_HDR and opcode 0 while no
+ *                      data message is open, or opcode 1 / 2 while one is: that
+ *                      record, 1002;
+ *   HVWS_C_CLOSE_BODY  sec. 5.5.1, 7.4: a complete control piece of opcode 8
+ *                      (HVWS_M_END and HVWS_M_CTL) whose len is 1 or above 125,
+ *                      or whose big-endian code (its first two bytes) is outside
+ *                      1000-1003, 1007-1011 and 3000-4999: the piece's rec, 1002;
+ *   HVWS_C_CLOSE_UTF8  such a piece of 3 .. 125 bytes whose bytes from the third
+ *                      on are not UTF-8 by hvws_utf8's machine (entered in
+ *                      ACCEPT, ACCEPT at the end): the piece's rec, 1007;
+ *   HVWS_C_TEXT_UTF8   the bad[s] of the last hvws_utf8 on ctx: that record,
+ *                      1007.  That hvws_utf8 must have run over the scan the
+ *                      message call ran over (no scan between them, the same
+ *                      segments), else HVWS_EINVAL;
+ *   HVWS_C_SIZE        with max_message > 0: a data record (opcode < 8) with
+ *                      HVWS_I_HDR whose `length` exceeds max_message: that
+ *                      record; or a data piece, open or complete, whose len
+ *                      exceeds it: the piece's rec; 1009.  The check by piece is
+ *                      batch-granular: a message that grows past the limit over
+ *                      several frames is failed at the last record its piece has
+ *                      in the batch in which it crossed, not at the frame that
+ *                      crossed.
+ * A piece whose rec is HVWS_MSG_NOREC takes the connection's first record
+ * index.  A Close piece of more than 125 bytes is judged from its len and never
+ * read; no read of a Close body leaves [off, off + len) rounded outwards to 16
+ * bytes and clipped to [0, out_cap) of the message call.
+ *
+ * The sequence rule walks connection s's records in frame-table order from
+ * HVWS_CK_OPEN of state_in[s].  Only records with HVWS_I_HDR and opcode 0, 1 or
+ * 2 matter: such a record is checked against the open bit and then SETS it to
+ * "FIN clear", whether or not it violated.  Opcodes 3-7 (the header class's)
+ * and control records leave it alone.  state_out's HVWS_CK_OPEN is the bit
+ * after the connection's last record.
+ *
+ * Verdict.  fail_rec[s] is the smallest record index at which an enabled class
+ * found a violation, HVWS_CHECK_NONE without one; why[s] the HVWS_C_* bits of
+ * all violations found at exactly that record; code[s] the close code of
+ * why[s]'s lowest set bit, 0 when nothing failed; state_out[s] is
+ * HVWS_CK_FAILED alone when fail_rec[s] is set.  What lies at or after the
+ * failing record does not change the verdict.
+ *
+ * hvws_get_check (waits; any pointer may be NULL) returns the four per
+ * connection of the last hvws_check; hvws_check_device is fail_rec[] in device
+ * memory (NULL: none yet), valid until the next hvws_check.
+ *
+ * hvws_replies_checked is hvws_replies after hvws_messages_rfc with one more
+ * rule: a piece whose rec >= fail_rec[s] of the last hvws_check produces no
+ * reply -- a CLOSE piece exactly at that record included: a Close that is itself
+ * malformed is not echoed.  Pieces before the failure reply as in hvws_replies,
+ * and an earlier CLOSE stays final.  A failed connection gets HVWS_RF_FAILED |
+ * HVWS_RF_CLOSED in its flags: the host appends the 4-byte frame 88 02 <code,
+ * big-endian> behind that connection's reply range (d_msg_off[first[s] +
+ * count[s]]) and closes the socket -- failures are rare and the host acts on the
+ * socket anyway.  HVWS_EINVAL unless hvws_check ran on the last message call.
+ * hvws_replies itself is unchanged.   */
+#define HVWS_C_HEADER     (1u << 0)
+#define HVWS_C_SEQUENCE   (1u << 1)
+#define HVWS_C_CLOSE_BODY (1u << 2)
+#define HVWS_C_CLOSE_UTF8 (1u << 3)
+#define HVWS_C_TEXT_UTF8  (1u << 4)
+#define HVWS_C_SIZE       (1u << 5)
+#define HVWS_C_ALL        0x3Fu
+#define HVWS_CK_OPEN      1u
+#define HVWS_CK_FAILED    2u
+#define HVWS_CHECK_NONE   UINT64_MAX
+#define HVWS_RF_FAILED    4u
+int hvws_check(hvws_ctx* ctx, uint32_t classes, uint64_t max_message, const uint32_t* state_in);
+int hvws_get_check(hvws_ctx* ctx, uint32_t* state_out, uint64_t* fail_rec, uint32_t* why, uint16_t* code);
+const uint64_t* hvws_check_device(hvws_ctx* ctx);   /* fail_rec[] in device memory */
+int hvws_replies_checked(hvws_ctx* ctx, uint32_t policy, const uint8_t* closed_in);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -88,6 +88,12 @@ assert TX_MSG_DTYPE.itemsize == 24
 R_PONG, R_CLOSE, R_ECHO = 1, 2, 4
 R_SERVER = R_PONG | R_CLOSE
 RF_CLOSED, RF_DEFERRED = 1, 2
+# HVWS_C_*, HVWS_CK_*, HVWS_CHECK_NONE and HVWS_RF_FAILED (hvws_check)
+C_HEADER, C_SEQUENCE, C_CLOSE_BODY, C_CLOSE_UTF8, C_TEXT_UTF8, C_SIZE = 1, 2, 4, 8, 16, 32
+C_ALL = 63
+CK_OPEN, CK_FAILED = 1, 2
+CHECK_NONE = (1 << 64) - 1
+RF_FAILED = 4
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -211,6 +217,12 @@ _SIGS = {
     ),
     "hvws_get_segment_replies": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_get_reply_flags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p]),
+    "hvws_get_check": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    ),
+    "hvws_check_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_replies_checked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -694,6 +706,38 @@ class Engine:
         out = np.zeros(max(nseg, 1), np.uint8)
         _check(lib().hvws_get_reply_flags(self.ctx, out.ctypes.data), "hvws_get_reply_flags")
         return out[:nseg]
+
+    def check(self, classes: int = C_ALL, max_message: int = 0, state_in=None) -> None:
+        """hvws_check over the last messages_rfc() call: which connections broke
+        the protocol (C_* classes), where and with which close code.  state_in:
+        one word per segment (CK_OPEN | CK_FAILED; None = all fresh).  No wait."""
+        st = None
+        if state_in is not None:
+            st = np.ascontiguousarray(state_in, dtype=np.uint32)
+        _check(lib().hvws_check(self.ctx, classes, max_message, st.ctypes.data if st is not None else None),
+               "hvws_check")
+
+    def check_result(self, nseg: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(state_out, fail_rec, why, code) per segment of the last check() call:
+        the word to carry into the connection's next batch, the first violating
+        record (CHECK_NONE if none), the classes violated there, the close code."""
+        st = np.zeros(max(nseg, 1), dtype=np.uint32)
+        fail = np.zeros(max(nseg, 1), dtype=np.uint64)
+        why = np.zeros(max(nseg, 1), dtype=np.uint32)
+        code = np.zeros(max(nseg, 1), dtype=np.uint16)
+        _check(lib().hvws_get_check(self.ctx, st.ctypes.data, fail.ctypes.data, why.ctypes.data, code.ctypes.data),
+               "hvws_get_check")
+        return st[:nseg], fail[:nseg], why[:nseg], code[:nseg]
+
+    def replies_checked(self, policy: int, closed_in=None) -> None:
+        """hvws_replies_checked: replies() with the last check()'s fail_rec as a
+        second limit -- nothing at or after a connection's failing record is
+        answered, and the connection's flags carry RF_FAILED | RF_CLOSED."""
+        ci = None
+        if closed_in is not None:
+            ci = np.ascontiguousarray(closed_in, dtype=np.uint8)
+        _check(lib().hvws_replies_checked(self.ctx, policy, ci.ctypes.data if ci is not None else None),
+               "hvws_replies_checked")
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

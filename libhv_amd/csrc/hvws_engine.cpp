@@ -287,6 +287,20 @@ struct hvws_ctx {
     bool have_rep = false;
     uint32_t rp_nseg = 0;
     uint64_t rp_cap = 0;
+    // hvws_check: the sequence scan's scratch, one byte of violation classes
+    // per record and piece, per-connection state in / out, fail_rec, why and
+    // code; state_in goes up as hvws_utf8's does.  scan_gen counts the scans of
+    // the context; u8_gen / mg_gen: the scan the last hvws_utf8 / message call
+    // ran over; msg_seq counts the message calls, ck_msg: the one checked.
+    dbuf ck_scan, ck_viol, ck_in, ck_out, ck_fail, ck_why, ck_code;
+    hbuf h_ck_in;
+    hipEvent_t ck_up_ev = nullptr;
+    bool ck_up_pending = false;
+    bool have_chk = false;
+    uint32_t ck_nseg = 0;
+    uint64_t scan_gen = 0, u8_gen = 0, mg_gen = 0, msg_seq = 0, ck_msg = 0;
+    const uint8_t* mg_dout = nullptr;   // the last message call's output and its capacity
+    uint64_t mg_out_cap = 0;
     // small-batch path (k_small): upload packet, record slots, pinned results
     hbuf h_small_in, h_small_out;
     hbuf h_small_done;             // per-segment completion words k_small writes last
@@ -1102,6 +1116,7 @@ int scan_device_carry(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, uint32_
     // The other table set: the previous batch's tables stay intact while its
     // unmask may still be running (pipelined steps).
     c->cur ^= 1;
+    ++c->scan_gen;   // hvws_check: the passes before this scan ran over another table
     c->prev_path = c->scan_path;
     c->run_active = false;
     if (c->cs == c->stream) c->piped = false;   // a later pipelined step re-arms the set events
@@ -1505,6 +1520,7 @@ int rx_batch_small(hvws_ctx* c, uint8_t* h_rx, uint64_t len, const hvws_segment*
     c->nfr_known = true;
     c->rx = nullptr;   // the device frame table is not populated: hvws_unmask refuses
     c->rx_len = 0;
+    ++c->scan_gen;
     c->have_scan = true;
     c->hcache_valid = true;
     if (carry) {
@@ -2317,7 +2333,8 @@ void hvws_ctx_destroy(hvws_ctx* c) {
                         &c->mg_in, &c->mg_out, &c->mg_meta, &c->mj_len, &c->mj_src, &c->mj_key, &c->mj_info, &c->mj_prow,
                         &c->mj_carry, &c->sd_scan, &c->sd_first, &c->sd_meta, &c->sd_poff,
                         &c->sd_len, &c->sd_flags, &c->sd_mask, &c->rp_scan, &c->rp_limit, &c->rp_msgs, &c->rp_piece,
-                        &c->rp_first, &c->rp_count, &c->rp_flags, &c->rp_closed})
+                        &c->rp_first, &c->rp_count, &c->rp_flags, &c->rp_closed, &c->ck_scan, &c->ck_viol, &c->ck_in,
+                        &c->ck_out, &c->ck_fail, &c->ck_why, &c->ck_code})
             b->release();
         c->chk.release();
     }
@@ -2332,6 +2349,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->h_u8_in.release();
         c->h_mg_in.release();
         c->h_rp_in.release();
+        c->h_ck_in.release();
         c->h_segs.release();
         for (hbuf& b : c->h_up) b.release();
         c->h_total.release();
@@ -2346,6 +2364,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         if (c->u8_up_ev) hipEventDestroy(c->u8_up_ev);
         if (c->mg_up_ev) hipEventDestroy(c->mg_up_ev);
         if (c->rp_up_ev) hipEventDestroy(c->rp_up_ev);
+        if (c->ck_up_ev) hipEventDestroy(c->ck_up_ev);
         for (hipEvent_t ev : c->pipe_ev)
             if (ev) hipEventDestroy(ev);
         for (auto& ev : c->ev)
@@ -2648,6 +2667,7 @@ int hvws_utf8(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, con
     }
     c->have_u8 = true;
     c->u8_nseg = nseg;
+    c->u8_gen = c->scan_gen;
     return HVWS_OK;
 }
 
@@ -2888,6 +2908,10 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     c->have_rfc = rfc;
     c->mg_nseg = nseg;
     c->mg_cap = ncap;
+    c->mg_gen = c->scan_gen;
+    ++c->msg_seq;
+    c->mg_dout = d_out;
+    c->mg_out_cap = out_cap;
     return HVWS_OK;
 }
 }  // namespace
@@ -3560,10 +3584,13 @@ int hvws_send_messages(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint
 
 // The server's onMessage dispatch over the last hvws_messages' pieces
 // (hvws_send.hip): no wait.
-int hvws_replies(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
+namespace {
+int replies_pass(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in, bool checked) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!c->have_msg) return set_err(HVWS_EINVAL, "hvws_replies without a preceding hvws_messages");
+    if (checked && (!c->have_rfc || !c->have_chk || c->ck_msg != c->msg_seq))
+        return set_err(HVWS_EINVAL, "hvws_replies_checked without an hvws_check of the last hvws_messages_rfc");
     if (policy & ~(uint32_t)(HVWS_R_PONG | HVWS_R_CLOSE | HVWS_R_ECHO))
         return set_err(HVWS_EINVAL, "hvws_replies: unknown policy bits");
     const uint32_t nseg = c->mg_nseg;
@@ -3593,12 +3620,111 @@ int hvws_replies(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
                           c->mg_count.as<uint64_t>(), nseg, policy, closed_in ? c->rp_closed.as<uint8_t>() : nullptr,
                           c->rp_limit.as<uint64_t>(), c->rp_scan.as<uint64_t>(), c->rp_msgs.as<dtxmsg>(),
                           c->rp_piece.as<uint64_t>(), c->rp_first.as<uint64_t>(), c->rp_count.as<uint64_t>(),
-                          c->rp_flags.as<uint8_t>(), c->have_rfc, c->stream),
+                          c->rp_flags.as<uint8_t>(), c->have_rfc, c->stream,
+                          checked ? c->ck_fail.as<uint64_t>() : nullptr),
            HVWS_EHIP);
     c->have_rep = true;
     c->rp_nseg = nseg;
     c->rp_cap = cap;
     return HVWS_OK;
+}
+}  // namespace
+
+int hvws_replies(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
+    return replies_pass(c, policy, closed_in, false);
+}
+
+// hvws_replies with hvws_check's fail_rec as a second per-connection limit.
+int hvws_replies_checked(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in) {
+    return replies_pass(c, policy, closed_in, true);
+}
+
+static_assert(CK_HEADER == HVWS_C_HEADER && CK_SEQUENCE == HVWS_C_SEQUENCE && CK_CLOSE_BODY == HVWS_C_CLOSE_BODY &&
+                  CK_CLOSE_UTF8 == HVWS_C_CLOSE_UTF8 && CK_TEXT_UTF8 == HVWS_C_TEXT_UTF8 && CK_SIZE == HVWS_C_SIZE &&
+                  CK_ALL == HVWS_C_ALL && CK_OPEN == HVWS_CK_OPEN && CK_FAILED == HVWS_CK_FAILED &&
+                  RF_FAILED == HVWS_RF_FAILED,
+              "check bits");
+
+// Which connections of the last hvws_messages_rfc must be failed, where and
+// why (hvws_check.hip): asynchronous on the context stream, no wait.
+int hvws_check(hvws_ctx* c, uint32_t classes, uint64_t max_message, const uint32_t* state_in) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_msg || !c->have_rfc) return set_err(HVWS_EINVAL, "hvws_check without a preceding hvws_messages_rfc");
+    if (c->mg_gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_check: a scan has run since hvws_messages_rfc");
+    if (classes & ~(uint32_t)HVWS_C_ALL) return set_err(HVWS_EINVAL, "hvws_check: unknown class bits");
+    const uint32_t nseg = c->mg_nseg;
+    if ((classes & HVWS_C_TEXT_UTF8) && (!c->have_u8 || c->u8_gen != c->scan_gen || c->u8_nseg != nseg))
+        return set_err(HVWS_EINVAL, "hvws_check: HVWS_C_TEXT_UTF8 without an hvws_utf8 over the same scan");
+    if (state_in)
+        for (uint32_t s = 0; s < nseg; ++s)
+            if (state_in[s] & ~(uint32_t)(HVWS_CK_OPEN | HVWS_CK_FAILED))
+                return set_err(HVWS_EINVAL, "hvws_check: state_in is no state hvws_get_check returns");
+    // the record bound hvws_messages_rfc ran with, or the count read since
+    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
+    const uint64_t pcap = c->mg_cap;
+    HIP_OR(c->ck_scan.ensure(check_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(c->ck_viol.ensure(cap + pcap + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck_in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck_out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck_fail.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck_why.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck_code.ensure((uint64_t)nseg * 2 + 16), HVWS_ENOMEM);
+    c->have_chk = false;   // the tables are being rewritten
+    if (state_in && nseg) {
+        if (!c->ck_up_ev) HIP_OR(hipEventCreateWithFlags(&c->ck_up_ev, hipEventDisableTiming), HVWS_EHIP);
+        if (c->ck_up_pending) {   // the previous pass's copy out of the slot
+            HIP_OR(hipEventSynchronize(c->ck_up_ev), HVWS_EHIP);
+            c->ck_up_pending = false;
+        }
+        HIP_OR(c->h_ck_in.ensure((uint64_t)nseg * 4), HVWS_ENOMEM);
+        memcpy(c->h_ck_in.p, state_in, (uint64_t)nseg * 4);
+        HIP_OR(hipMemcpyAsync(c->ck_in.p, c->h_ck_in.p, (uint64_t)nseg * 4, hipMemcpyHostToDevice, c->stream),
+               HVWS_EHIP);
+        HIP_OR(hipEventRecord(c->ck_up_ev, c->stream), HVWS_EHIP);
+        c->ck_up_pending = true;
+    }
+    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    HIP_OR(launch_check(c->T().f_info.as<uint32_t>(), c->T().f_length.as<uint64_t>(), c->T().total.as<uint64_t>(), cap,
+                        c->T().bases.as<uint64_t>(), nseg, c->mg_msgs.as<dmsg>(), c->mg_meta.as<uint64_t>(), pcap,
+                        c->mg_dout, c->mg_out_cap, c->u8_bad.as<uint64_t>(), classes, max_message,
+                        state_in ? c->ck_in.as<uint32_t>() : nullptr, c->ck_scan.p, c->ck_viol.as<uint8_t>(),
+                        c->ck_out.as<uint32_t>(), c->ck_fail.as<uint64_t>(), c->ck_why.as<uint32_t>(),
+                        c->ck_code.as<uint16_t>(), c->stream),
+           HVWS_EHIP);
+    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
+    c->ev_build = true;
+    // Pipelined steps: the scan two steps on writes this table set and must
+    // wait for this pass as it waits for the set's unmask.
+    if (c->piped) {
+        HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
+        c->T().free_wait = c->T().free_ev;
+        c->T().free_pending = true;
+    }
+    c->have_chk = true;
+    c->ck_nseg = nseg;
+    c->ck_msg = c->msg_seq;
+    return HVWS_OK;
+}
+
+int hvws_get_check(hvws_ctx* c, uint32_t* state_out, uint64_t* fail_rec, uint32_t* why, uint16_t* code) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (!c->have_chk) return set_err(HVWS_EINVAL, "no hvws_check call yet");
+    const uint64_t nseg = c->ck_nseg;
+    if (state_out && nseg)
+        HIP_OR(hipMemcpyAsync(state_out, c->ck_out.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (fail_rec && nseg)
+        HIP_OR(hipMemcpyAsync(fail_rec, c->ck_fail.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (why && nseg) HIP_OR(hipMemcpyAsync(why, c->ck_why.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    if (code && nseg) HIP_OR(hipMemcpyAsync(code, c->ck_code.p, nseg * 2, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+const uint64_t* hvws_check_device(hvws_ctx* c) {
+    if (!c || !c->have_chk) return nullptr;
+    return c->ck_fail.as<uint64_t>();
 }
 
 const hvws_tx_msg* hvws_replies_device(hvws_ctx* c) {

@@ -583,7 +583,7 @@ struct dtxmsg {
     uint64_t off, len;
     uint32_t flags, key;
 };
-enum : uint32_t { R_PONG = 1u, R_CLOSE = 2u, R_ECHO = 4u, RF_CLOSED = 1u, RF_DEFERRED = 2u };
+enum : uint32_t { R_PONG = 1u, R_CLOSE = 2u, R_ECHO = 4u, RF_CLOSED = 1u, RF_DEFERRED = 2u, RF_FAILED = 4u };
 uint64_t send_scratch_bytes(uint64_t n);
 // The message pass over msgs[0 .. min(*n_dev, n)) (n_dev may be null), F bytes
 // per fragment: scratch (send_scratch_bytes(n)) keeps each message's frames and
@@ -604,11 +604,33 @@ hipError_t launch_send_expand(const dtxmsg* msgs, const void* scratch, const uin
 // bytes or null; limit: nseg words; scratch: rep_scratch_words(cap) words, of
 // which word `cap` receives the reply count; out / piece: cap entries.  by_rec:
 // the table is hvws_messages_rfc's, "close is final" goes by the pieces' rec.
+// fail (nseg words of hvws_check's fail_rec, or null; by_rec only): a piece
+// whose rec is at or beyond its connection's word sends nothing, and a
+// connection whose word is set gets RF_FAILED | RF_CLOSED.
 uint64_t rep_scratch_words(uint64_t cap);
 hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t cap, const uint64_t* seg_first,
                           const uint64_t* seg_count, uint32_t nseg, uint32_t policy, const uint8_t* closed_in,
                           uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
-                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st);
+                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st,
+                          const uint64_t* fail = nullptr);
+// hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
+// table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
+// table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125
+// bytes per Close piece of that call's output out[0, out_len), and u8_bad (the
+// bad[] of hvws_utf8; read only with CK_TEXT_UTF8).  scratch:
+// check_scratch_bytes(cap); viol: cap + pcap bytes; state_in (device, nullptr:
+// all fresh) -> state_out, fail, why, code (nseg entries each).
+enum : uint32_t {
+    CK_HEADER = 1u, CK_SEQUENCE = 2u, CK_CLOSE_BODY = 4u, CK_CLOSE_UTF8 = 8u, CK_TEXT_UTF8 = 16u, CK_SIZE = 32u,
+    CK_ALL = 63u,
+    CK_OPEN = 1u, CK_FAILED = 2u   // the state word
+};
+uint64_t check_scratch_bytes(uint64_t cap);
+hipError_t launch_check(const uint32_t* info, const uint64_t* length, const uint64_t* nfr_dev, uint64_t cap,
+                        const uint64_t* bases, uint32_t nseg, const dmsg* msgs, const uint64_t* mg_meta, uint64_t pcap,
+                        const uint8_t* out, uint64_t out_len, const uint64_t* u8_bad, uint32_t classes,
+                        uint64_t max_message, const uint32_t* state_in, void* scratch, uint8_t* viol, uint32_t* state_out,
+                        uint64_t* fail, uint32_t* why, uint16_t* code, hipStream_t st);
 // Predicted frames above which a uniform segment is verified grid-wide (k_verify).
 uint64_t spec_min();
 uint64_t set_spec_min(uint64_t v);   // 0 = default; returns the previous value

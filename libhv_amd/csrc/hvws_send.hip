@@ -29,6 +29,8 @@
 // 174-200) over the piece table of hvws_messages: each segment's first closing
 // piece (one atomic min per closing piece -- closes are rare), then flag, scan
 // and scatter into a dense table of hvws_tx_msg the send reads in place.
+// hvws_replies_checked adds hvws_check's fail_rec as a second per-segment limit
+// (rep_load::fail; null for hvws_replies, whose branches are then the old ones).
 //
 // Traffic: 24 B read + 32 B of scan state per message, ~37 B written per frame;
 // per piece 40 B read twice and 32 B written per reply.
@@ -210,11 +212,15 @@ struct rep_load {
     uint32_t policy;
     const unsigned long long* limit;
     uint32_t by_rec;
+    // hvws_replies_checked: hvws_check's fail_rec per segment, a second limit by
+    // rec (a CLOSE exactly there is itself malformed: not echoed); else null
+    const unsigned long long* fail;
     __device__ __forceinline__ uint64_t operator()(uint64_t p) const {
         if (p >= rep_pieces(mg_meta, cap)) return 0;
         const dmsg m = msgs[p];
         const uint32_t op = reply_op(m.info, policy);
         if (!op || m.total != m.len) return 0;
+        if (fail && m.rec >= fail[m.seg]) return 0;
         const unsigned long long lim = limit[m.seg];
         if (by_rec) return m.rec + 1 < lim || (m.rec + 1 == lim && op == 8) ? 1u : 0u;
         return p < lim ? 1u : 0u;
@@ -248,6 +254,7 @@ __global__ __launch_bounds__(256) void k_rep_segs(rep_load in, const uint64_t* _
     rep_count[s] = b - a;
     const unsigned long long lim = in.limit[s];
     uint32_t fl = lim != ~0ull ? RF_CLOSED : 0u;
+    if (in.fail && in.fail[s] != ~0ull) fl |= RF_FAILED | RF_CLOSED;
     if (cnt && lim > p0 && !in.by_rec) {   // only a segment's first piece can complete an earlier batch's message
         const dmsg m = in.msgs[p0];
         if (reply_op(m.info, in.policy) && m.total != m.len) fl |= RF_DEFERRED;
@@ -289,7 +296,7 @@ uint64_t rep_scratch_words(uint64_t cap) { return cap + 16 + scan_tmp_words(cap)
 hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t cap, const uint64_t* seg_first,
                           const uint64_t* seg_count, uint32_t nseg, uint32_t policy, const uint8_t* closed_in,
                           uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
-                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st) {
+                          uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st, const uint64_t* fail) {
     unsigned long long* lim = reinterpret_cast<unsigned long long*>(limit);
     uint64_t* ex = scratch;
     uint64_t* total = ex + cap;   // the reply count: the send's d_n
@@ -300,7 +307,8 @@ hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t ca
                                lim);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const rep_load in{msgs, mg_meta, cap, policy, lim, by_rec ? 1u : 0u};
+    const rep_load in{msgs, mg_meta, cap, policy, lim, by_rec ? 1u : 0u,
+                      reinterpret_cast<const unsigned long long*>(fail)};
     e = launch_scan_of(in, ex, cap, tmp, total, st);
     if (e != hipSuccess) return e;
     if (pb) hipLaunchKernelGGL(k_rep_scatter, dim3(pb), dim3(256), 0, st, in, ex, out, piece);
