@@ -966,7 +966,10 @@ uint64_t hvws_set_door_idle_us(uint64_t us);
  * to fd the state of every context -- each resident worker's mailbox (seq,
  * done, alive, exited epoch) and the host's view of it, then
  * hipStreamQuery of every stream of the context (a query can itself block
- * behind a stuck runtime call; the memory state is written first). */
+ * behind a stuck runtime call; the memory state is written first).  The first
+ * line ends with "holding D device bytes, P pinned bytes": what the library's
+ * contexts hold in their grow-only buffers, process-wide -- a destroyed
+ * context leaves neither behind. */
 int hvws_debug_dump(int fd);
 /* Diagnostics: a native backtrace of every thread of the process to fd
  * (SIGUSR2 to each thread in turn, backtrace_symbols_fd in the handler).

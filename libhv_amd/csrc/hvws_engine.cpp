@@ -53,21 +53,20 @@ int set_err(int code, const char* fmt, ...) {
 // whichever thread owns it (defined with the worker).
 void door_park_device();
 
+// Device and pinned bytes currently held through dbuf / hbuf, process-wide
+// (hvws_debug_dump prints them: a destroyed context leaves neither behind).
+std::atomic<uint64_t> g_dev_bytes{0}, g_pin_bytes{0};
+
 // Grow-only device allocation.
 struct dbuf {
     void* p = nullptr;
     uint64_t cap = 0;
     hipError_t ensure(uint64_t bytes) {
         if (bytes <= cap && p) return hipSuccess;
-        if (p) {
-            door_park_device();
-            hipFree(p);
-        }
-        p = nullptr;
-        cap = 0;
+        release();
         uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 4096);
         hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) g_dev_bytes += (cap = want);
         return e;
     }
     // ensure(), with a new allocation zeroed on st (arrays the kernels leave zero between uses)
@@ -81,6 +80,7 @@ struct dbuf {
         if (p) {
             door_park_device();
             hipFree(p);
+            g_dev_bytes -= cap;
         }
         p = nullptr;
         cap = 0;
@@ -96,22 +96,17 @@ struct hbuf {   // grow-only pinned host allocation
     unsigned flags = hipHostMallocDefault;   // hipHostMallocCoherent: device reads/writes bypass its caches
     hipError_t ensure(uint64_t bytes) {
         if (bytes <= cap && p) return hipSuccess;
-        if (p) {
-            door_park_device();
-            hipHostFree(p);
-        }
-        p = nullptr;
-        dev = nullptr;
-        cap = 0;
+        release();
         uint64_t want = std::max<uint64_t>(bytes + bytes / 2, 4096);
         hipError_t e = hipHostMalloc(&p, want, flags);
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) g_pin_bytes += (cap = want);
         return e;
     }
     void release() {
         if (p) {
             door_park_device();
             hipHostFree(p);
+            g_pin_bytes -= cap;
         }
         p = nullptr;
         dev = nullptr;
@@ -119,6 +114,47 @@ struct hbuf {   // grow-only pinned host allocation
     }
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+void free_all(std::initializer_list<dbuf*> l) {
+    for (dbuf* b : l) b->release();
+}
+
+// Which part of a context's memory a release() frees: hvws_ctx_destroy runs
+// the device frees, then the pinned frees, then the event destroys.
+enum rel { REL_DEVICE, REL_PINNED, REL_EVENTS };
+
+// A pass's per-connection input on its way up: a pinned slot, reusable once
+// the copy that read it has run (the event, created on first use), so a pass
+// never waits for the previous pass's kernels.
+struct up_slot {
+    hbuf h;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    // a (na bytes), then b (nb bytes) behind it, to dst in one copy on st;
+    // nothing at all without a or without bytes
+    int send(void* dst, hipStream_t st, const void* a, uint64_t na, const void* b = nullptr, uint64_t nb = 0) {
+        if (!a || !na) return HVWS_OK;
+        if (!ev) HIP_OR(hipEventCreateWithFlags(&ev, hipEventDisableTiming), HVWS_EHIP);
+        if (pending) {   // the previous pass's copy out of the slot
+            HIP_OR(hipEventSynchronize(ev), HVWS_EHIP);
+            pending = false;
+        }
+        HIP_OR(h.ensure(na + nb), HVWS_ENOMEM);
+        memcpy(h.p, a, na);
+        if (nb) memcpy(h.as<uint8_t>() + na, b, nb);
+        HIP_OR(hipMemcpyAsync(dst, h.p, na + nb, hipMemcpyHostToDevice, st), HVWS_EHIP);
+        HIP_OR(hipEventRecord(ev, st), HVWS_EHIP);
+        pending = true;
+        return HVWS_OK;
+    }
+    void release(rel ph) {
+        if (ph == REL_PINNED) h.release();
+        if (ph == REL_EVENTS && ev) {
+            hipEventDestroy(ev);
+            ev = nullptr;
+        }
+    }
 };
 
 }  // namespace
@@ -145,11 +181,117 @@ struct tset {
                                     // event attached to the unmask's own dispatch (no marker packet)
     bool free_pending = false;
     void release() {
-        for (dbuf* b : {&carry_out, &counts, &bases, &total, &sc_mid, &sc_npred, &sc_pbase, &sc_fail, &sc_masked,
-                        &sc_total, &sc_est, &f_hdr, &f_off, &f_len, &f_length, &f_key, &f_keyrot, &f_info,
-                        &tile_first, &tile_key, &tile_kind, &runs, &run_fail, &run_trun})
-            b->release();
+        free_all({&carry_out, &counts, &bases, &total, &sc_mid, &sc_npred, &sc_pbase, &sc_fail, &sc_masked, &sc_total,
+                  &sc_est, &f_hdr, &f_off, &f_len, &f_length, &f_key, &f_keyrot, &f_info, &tile_first, &tile_key,
+                  &tile_kind, &runs, &run_fail, &run_trun});
         frame_cap = 0;
+    }
+};
+
+// State of one table pass each (and of the transmit side): its device
+// buffers, its upload slot, what its last call left.  release() lists exactly
+// the members declared above it.
+
+// hvws_utf8: per-record words and interior flags (zero between passes), its
+// tile index, {record count}, per-segment state in / out and verdicts;
+// state_in goes up through the slot.  gen: the scan (scan_gen) it ran over.
+struct pass_u8 {
+    dbuf words, flags, tiles, meta, in, out, bad;
+    up_slot up;
+    bool have = false;
+    uint32_t nseg = 0;
+    uint64_t gen = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&words, &flags, &tiles, &meta, &in, &out, &bad});
+        up.release(ph);
+    }
+};
+
+// hvws_messages: the scan's scratch, out_off per record, the tile index over
+// the output, the piece table, per-segment first / count, state in / out,
+// {records, payload bytes, pieces}; state_in goes up through the slot.
+// hvws_messages_joined: the row table (length, source, key, info per row),
+// each piece's last row, each segment's carry offset; prev_off goes up behind
+// state_in in the same slot.
+// hvws_messages_rfc: the class scan's scratch, each row's record, each
+// virtual connection's carried row and record count; the states go up
+// repacked (2 per connection, then their offsets: rf_st, rf_off) and come
+// back as hvws_rfc_state in `out`.
+struct pass_msg {
+    dbuf scan, off, tiles, msgs, first, count, in, out, meta;
+    dbuf row_len, row_src, row_key, row_info, prow, carry;
+    dbuf cls, rec, vbase, vcnt;
+    up_slot up;
+    std::vector<hvws_msg_state> rf_st;
+    std::vector<uint64_t> rf_off;
+    bool have = false;
+    bool joined = false;   // the last call was the joined form
+    bool rfc = false;      // ... the RFC form
+    uint32_t nseg = 0;
+    uint64_t cap = 0;   // the piece bound of the last call (its record capacity; joined: its rows)
+    uint64_t gen = 0;   // the scan it ran over
+    uint64_t seq = 0;   // message calls so far
+    const uint8_t* dout = nullptr;   // the last call's output and its capacity
+    uint64_t out_cap = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE)
+            free_all({&scan, &off, &tiles, &msgs, &first, &count, &in, &out, &meta, &row_len, &row_src, &row_key,
+                      &row_info, &prow, &carry, &cls, &rec, &vbase, &vcnt});
+        up.release(ph);
+    }
+};
+
+// hvws_send_messages: the message scan's scratch, each message's first frame,
+// {frames, bytes, bad, count, uniform layout}, and the per-frame rows k_build
+// reads (out_off and size in pass_tx's off / size)
+struct pass_send {
+    dbuf scan, first, meta, poff, len, flags, mask;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &first, &meta, &poff, &len, &flags, &mask});
+    }
+};
+
+// hvws_replies: the scan's scratch (word `cap` of it: the reply count), each
+// segment's closing limit, the reply table and the piece each reply answers,
+// per-segment first / count / flags; closed_in goes up through the slot
+struct pass_replies {
+    dbuf scan, limit, msgs, piece, first, count, flags, closed;
+    up_slot up;
+    bool have = false;
+    uint32_t nseg = 0;
+    uint64_t cap = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &limit, &msgs, &piece, &first, &count, &flags, &closed});
+        up.release(ph);
+    }
+};
+
+// hvws_check: the sequence scan's scratch, one byte of violation classes per
+// record and piece, per-connection state in / out, fail_rec, why and code;
+// state_in goes up through the slot.  msg: the message call (pass_msg::seq)
+// it checked.
+struct pass_check {
+    dbuf scan, viol, in, out, fail, why, code;
+    up_slot up;
+    bool have = false;
+    uint32_t nseg = 0;
+    uint64_t msg = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &viol, &in, &out, &fail, &why, &code});
+        up.release(ph);
+    }
+};
+
+// transmit side (hvws_build_frames; hvws_send_messages reads its counts
+// through h as well)
+struct pass_tx {
+    dbuf size, off, scan, tiles, stat, span;
+    hbuf h;
+    int variant = 0;        // k_build geometry of the last build
+    bool uniform = false;   // ... and whether it built a uniform layout without a tile index
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&size, &off, &scan, &tiles, &stat, &span});
+        if (ph == REL_PINNED) h.release();
     }
 };
 
@@ -240,67 +382,17 @@ struct hvws_ctx {
     dbuf stage;
     dbuf xor_stage;
     dbuf synth_sizes, synth_tiles, synth_bad;
-    // hvws_utf8: per-record words and interior flags (zero between passes),
-    // its tile index, {record count}, per-segment state in / out and verdicts;
-    // state_in goes up through a pinned slot, reusable once its copy has run
-    dbuf u8_words, u8_flags, u8_tiles, u8_meta, u8_in, u8_out, u8_bad;
-    hbuf h_u8_in;
-    hipEvent_t u8_up_ev = nullptr;
-    bool u8_up_pending = false;
-    bool have_u8 = false;
-    uint32_t u8_nseg = 0;
-    // hvws_messages: the scan's scratch, out_off per record, the tile index
-    // over the output, the piece table, per-segment first / count, state in /
-    // out, {records, payload bytes, pieces}; state_in goes up as hvws_utf8's does
-    dbuf mg_scan, mg_off, mg_tiles, mg_msgs, mg_first, mg_count, mg_in, mg_out, mg_meta;
-    hbuf h_mg_in;
-    hipEvent_t mg_up_ev = nullptr;
-    bool mg_up_pending = false;
-    bool have_msg = false;
-    uint32_t mg_nseg = 0;
-    uint64_t mg_cap = 0;   // the piece bound of the last hvws_messages (its record capacity; joined: its rows)
-    // hvws_messages_joined: the row table (length, source, key, info per row),
-    // each piece's last row, each segment's carry offset; prev_off goes up
-    // behind state_in in the same slot
-    dbuf mj_len, mj_src, mj_key, mj_info, mj_prow, mj_carry;
-    bool have_join = false;   // the last hvws_messages was the joined form
-    // hvws_messages_rfc: the class scan's scratch, each row's record, each
-    // virtual connection's carried row and record count; the states go up
-    // repacked (2 per connection, then their offsets) and come back as
-    // hvws_rfc_state in mg_out
-    dbuf mr_cls, mr_rec, mr_vbase, mr_vcnt;
-    std::vector<hvws_msg_state> rf_st;
-    std::vector<uint64_t> rf_off;
-    bool have_rfc = false;   // the last hvws_messages was the RFC form
-    // hvws_send_messages: the message scan's scratch, each message's first
-    // frame, {frames, bytes, bad, count, uniform layout}, and the per-frame rows
-    // k_build reads (out_off and size in tx_off / tx_size)
-    dbuf sd_scan, sd_first, sd_meta, sd_poff, sd_len, sd_flags, sd_mask;
-    // hvws_replies: the scan's scratch (word rp_cap of it: the reply count),
-    // each segment's closing limit, the reply table and the piece each reply
-    // answers, per-segment first / count / flags; closed_in goes up as
-    // hvws_messages' state_in does
-    dbuf rp_scan, rp_limit, rp_msgs, rp_piece, rp_first, rp_count, rp_flags, rp_closed;
-    hbuf h_rp_in;
-    hipEvent_t rp_up_ev = nullptr;
-    bool rp_up_pending = false;
-    bool have_rep = false;
-    uint32_t rp_nseg = 0;
-    uint64_t rp_cap = 0;
-    // hvws_check: the sequence scan's scratch, one byte of violation classes
-    // per record and piece, per-connection state in / out, fail_rec, why and
-    // code; state_in goes up as hvws_utf8's does.  scan_gen counts the scans of
-    // the context; u8_gen / mg_gen: the scan the last hvws_utf8 / message call
-    // ran over; msg_seq counts the message calls, ck_msg: the one checked.
-    dbuf ck_scan, ck_viol, ck_in, ck_out, ck_fail, ck_why, ck_code;
-    hbuf h_ck_in;
-    hipEvent_t ck_up_ev = nullptr;
-    bool ck_up_pending = false;
-    bool have_chk = false;
-    uint32_t ck_nseg = 0;
-    uint64_t scan_gen = 0, u8_gen = 0, mg_gen = 0, msg_seq = 0, ck_msg = 0;
-    const uint8_t* mg_dout = nullptr;   // the last message call's output and its capacity
-    uint64_t mg_out_cap = 0;
+    // The table passes behind a scan, and the transmit side: one struct each
+    // (pass_u8 .. pass_tx above), which declares the pass's buffers and
+    // releases them.  scan_gen counts the scans of the context.
+    pass_u8 u8;
+    pass_msg mg;
+    pass_send sd;
+    pass_replies rp;
+    pass_check ck;
+    pass_tx tx;
+    uint64_t scan_gen = 0;
+    bool ev_build = false;   // ev[4] .. ev[5] hold a timed region (hvws_last_kernel_ms)
     // small-batch path (k_small): upload packet, record slots, pinned results
     hbuf h_small_in, h_small_out;
     hbuf h_small_done;             // per-segment completion words k_small writes last
@@ -318,12 +410,6 @@ struct hvws_ctx {
     int small_zc = 1;              // $HVWS_EXPERIMENT small_zc / hvws_set_small_zero_copy
     uint64_t zc_batch = kZcBatch;  // largest zero-copy batch ($HVWS_EXPERIMENT zc_batch)
     uint32_t vmask = 0;         // protocol validation classes (V_*); 0 = reference behaviour
-    // transmit side (hvws_build_frames)
-    dbuf tx_size, tx_off, tx_scan, tx_tiles, tx_stat, tx_span;
-    hbuf h_tx;
-    bool ev_build = false;
-    int tx_variant = 0;   // k_build geometry of the last hvws_build_frames
-    bool tx_uniform = false;   // ... and whether it built a uniform layout without a tile index
     // last scan
     uint32_t nseg = 0;
     uint64_t nfr = 0;
@@ -460,6 +546,69 @@ int check_batch_args(hvws_ctx* c, const uint8_t* d_rx, const hvws_segment* segs,
     if (!segs && nseg) return set_err(HVWS_EINVAL, "null segment table");
     if (((uintptr_t)d_rx & 15u) != 0) return set_err(HVWS_EINVAL, "rx buffer must be 16-byte aligned");
     return HVWS_OK;
+}
+
+// ---- what the table passes behind a scan share (hvws_utf8, messages_pass, hvws_check, ...)
+
+// `who` runs over the last scan's tables: there is one, of this very buffer.
+int behind_scan(hvws_ctx* c, const char* who, const uint8_t* d_rx, uint64_t rx_len) {
+    if (!c->have_scan) return set_err(HVWS_EINVAL, "%s without a preceding hvws_scan", who);
+    if (!d_rx || d_rx != c->rx || rx_len != c->rx_len)
+        return set_err(HVWS_EINVAL, "%s buffer differs from the scanned one", who);
+    return HVWS_OK;
+}
+
+// Records a pass sizes its tables for: c->nfr is the record count, or its
+// bound while the count is on the device.
+uint64_t record_bound(hvws_ctx* c) { return std::min<uint64_t>(c->nfr, c->T().frame_cap); }
+
+// The device work hvws_last_kernel_ms times: between these two.
+hipError_t timed_begin(hvws_ctx* c) { return hipEventRecord(c->ev[4], c->stream); }
+hipError_t timed_end(hvws_ctx* c) {
+    const hipError_t e = hipEventRecord(c->ev[5], c->stream);
+    if (e == hipSuccess) c->ev_build = true;
+    return e;
+}
+
+// Pipelined steps: the scan two steps on writes the current table set and
+// must wait for the pass queued so far as it waits for the set's unmask.
+hipError_t hold_tables(hvws_ctx* c) {
+    if (!c->piped) return hipSuccess;
+    tset& t = c->T();
+    const hipError_t e = hipEventRecord(t.free_ev, c->stream);
+    if (e != hipSuccess) return e;
+    t.free_wait = t.free_ev;
+    t.free_pending = true;
+    return hipSuccess;
+}
+
+// Rows to the host on the context stream -- a null dst or no bytes: skipped --
+// then one wait.
+struct d2h_row {
+    void* dst;
+    const void* src;
+    uint64_t bytes;
+};
+int read_rows(hvws_ctx* c, std::initializer_list<d2h_row> rows) {
+    for (const d2h_row& r : rows)
+        if (r.dst && r.bytes)
+            HIP_OR(hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
+    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    return HVWS_OK;
+}
+
+// One device word to the host; waits.
+hipError_t read_word(hvws_ctx* c, const uint64_t* src, uint64_t* v) {
+    const hipError_t e = hipMemcpyAsync(v, src, 8, hipMemcpyDeviceToHost, c->stream);
+    return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+// ... as the count `who` returns: -1, and the error set, when the read fails
+int64_t read_count(hvws_ctx* c, const uint64_t* src, const char* who) {
+    uint64_t n = 0;
+    if (read_word(c, src, &n) == hipSuccess) return (int64_t)n;
+    set_err(HVWS_EHIP, "%s: reading the count failed", who);
+    return -1;
 }
 
 // Device address of a pinned host buffer.
@@ -2137,7 +2286,9 @@ int hvws_debug_dump(int fd) {
         std::lock_guard<std::mutex> lk(g_ctx_m);
         all = g_ctx_all;
     }
-    dprintf(fd, "libhvws: %zu contexts, %d with a worker stream\n", all.size(), g_door_count.load());
+    dprintf(fd, "libhvws: %zu contexts, %d with a worker stream; holding %llu device bytes, %llu pinned bytes\n",
+            all.size(), g_door_count.load(), (unsigned long long)g_dev_bytes.load(),
+            (unsigned long long)g_pin_bytes.load());
     // memory state first (no HIP call, no lock a stuck caller could hold)
     for (hvws_ctx* c : all) {
         dprintf(fd, "  ctx %p dev %d door_mode %d door_live %d door_seq %llu epoch %llu launches %llu calls %llu",
@@ -2305,6 +2456,14 @@ void hvws_ctx_destroy(hvws_ctx* c) {
     // Each runtime call of the teardown is named while it runs (c->at): a
     // teardown that hangs names its call in the wedge report and
     // hvws_debug_dump (round 5: the r4k hang was inside this teardown).
+    const auto passes = [c](rel ph) {   // each pass releases what it declares, phase by phase
+        c->u8.release(ph);
+        c->mg.release(ph);
+        c->sd.release(ph);
+        c->rp.release(ph);
+        c->ck.release(ph);
+        c->tx.release(ph);
+    };
     {
         in_call ic(c, "hipStreamSynchronize(stream)");
         if (c->stream) hipStreamSynchronize(c->stream);
@@ -2319,41 +2478,29 @@ void hvws_ctx_destroy(hvws_ctx* c) {
     }
     {
         in_call ic(c, "hipFree (scratch, sieve, pipeline, staging)");
-        for (dbuf* b : {&c->sl_hdr, &c->sl_off, &c->sl_len, &c->sl_length, &c->sl_key, &c->sl_keyrot, &c->sl_info, &c->sl_bx})
-            b->release();
-        for (dbuf* b : {&c->sv_state, &c->sv_tcount, &c->sv_tbase, &c->sv_slot, &c->sv_pool, &c->sv_keep, &c->sv_kbase,
-                        &c->sv_Spre, &c->sv_S, &c->sv_J0, &c->sv_J1,
-                        &c->sv_mark, &c->sv_hops, &c->sv_rank, &c->sv_cnt, &c->sv_tmp, &c->sv_scr})
-            b->release();
-        for (dbuf* b : {&c->pipe_slot[0], &c->pipe_slot[1], &c->pipe_slot[2], &c->pipe_segs}) b->release();
-        for (dbuf* b : {&c->segs, &c->carry_in, &c->stage, &c->xor_stage, &c->synth_sizes, &c->synth_tiles, &c->synth_bad,
-                        &c->tx_size, &c->tx_off, &c->tx_scan, &c->tx_tiles, &c->tx_stat, &c->tx_span, &c->d_small_in,
-                        &c->d_small_slots, &c->u8_words, &c->u8_flags, &c->u8_tiles, &c->u8_meta, &c->u8_in, &c->u8_out,
-                        &c->u8_bad, &c->mg_scan, &c->mg_off, &c->mg_tiles, &c->mg_msgs, &c->mg_first, &c->mg_count,
-                        &c->mg_in, &c->mg_out, &c->mg_meta, &c->mj_len, &c->mj_src, &c->mj_key, &c->mj_info, &c->mj_prow,
-                        &c->mj_carry, &c->sd_scan, &c->sd_first, &c->sd_meta, &c->sd_poff,
-                        &c->sd_len, &c->sd_flags, &c->sd_mask, &c->rp_scan, &c->rp_limit, &c->rp_msgs, &c->rp_piece,
-                        &c->rp_first, &c->rp_count, &c->rp_flags, &c->rp_closed, &c->ck_scan, &c->ck_viol, &c->ck_in,
-                        &c->ck_out, &c->ck_fail, &c->ck_why, &c->ck_code})
-            b->release();
+        free_all({&c->sl_hdr, &c->sl_off, &c->sl_len, &c->sl_length, &c->sl_key, &c->sl_keyrot, &c->sl_info, &c->sl_bx});
+        free_all({&c->sv_state, &c->sv_tcount, &c->sv_tbase, &c->sv_slot, &c->sv_pool, &c->sv_keep, &c->sv_kbase,
+                  &c->sv_Spre, &c->sv_S, &c->sv_J0, &c->sv_J1, &c->sv_mark, &c->sv_hops, &c->sv_rank, &c->sv_cnt,
+                  &c->sv_tmp, &c->sv_scr});
+        free_all({&c->pipe_slot[0], &c->pipe_slot[1], &c->pipe_slot[2], &c->pipe_segs});
+        free_all({&c->segs, &c->carry_in, &c->stage, &c->xor_stage, &c->synth_sizes, &c->synth_tiles, &c->synth_bad,
+                  &c->d_small_in, &c->d_small_slots, &c->d_small_ctr});
+        passes(REL_DEVICE);
         c->chk.release();
     }
     {
         in_call ic(c, "hipHostFree (pinned buffers)");
         c->h_sv.release();
-        c->h_tx.release();
         c->h_small_in.release();
         c->h_small_done.release();
         c->h_small_out.release();
         c->h_feed.release();
-        c->h_u8_in.release();
-        c->h_mg_in.release();
-        c->h_rp_in.release();
-        c->h_ck_in.release();
+        passes(REL_PINNED);
         c->h_segs.release();
         for (hbuf& b : c->h_up) b.release();
         c->h_total.release();
         c->h_chk.release();
+        c->h_readback.release();
         c->h_status.release();
     }
     {
@@ -2361,10 +2508,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         for (tset& t : c->ts)
             if (t.free_ev) hipEventDestroy(t.free_ev);
         if (c->sv_ev) hipEventDestroy(c->sv_ev);
-        if (c->u8_up_ev) hipEventDestroy(c->u8_up_ev);
-        if (c->mg_up_ev) hipEventDestroy(c->mg_up_ev);
-        if (c->rp_up_ev) hipEventDestroy(c->rp_up_ev);
-        if (c->ck_up_ev) hipEventDestroy(c->ck_up_ev);
+        passes(REL_EVENTS);
         for (hipEvent_t ev : c->pipe_ev)
             if (ev) hipEventDestroy(ev);
         for (auto& ev : c->ev)
@@ -2615,98 +2759,62 @@ int hvws_unmask(hvws_ctx* c, uint8_t* d_rx, uint64_t rx_len) { return unmask_imp
 int hvws_utf8(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked, const uint32_t* state_in) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_utf8 without a preceding hvws_scan");
-    if (!d_rx || d_rx != c->rx || rx_len != c->rx_len)
-        return set_err(HVWS_EINVAL, "hvws_utf8 buffer differs from the scanned one");
+    if ((rc = behind_scan(c, "hvws_utf8", d_rx, rx_len)) != HVWS_OK) return rc;
     // a RUN step left no frame table: build it now (as hvws_unmask does)
     if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
     const uint32_t nseg = c->nseg;
-    // c->nfr: the record count, or its bound while the count is on the device
-    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
+    const uint64_t cap = record_bound(c);
     const uint64_t ntiles = (rx_len + U8_TILE - 1) / U8_TILE;
-    HIP_OR(c->u8_words.ensure(cap * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->u8_flags.ensure_zeroed(cap * 4 + 16, c->stream), HVWS_ENOMEM);
-    HIP_OR(c->u8_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
-    HIP_OR(c->u8_meta.ensure(64), HVWS_ENOMEM);
-    HIP_OR(c->u8_in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->u8_out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->u8_bad.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    if (state_in && nseg) {
-        if (!c->u8_up_ev) HIP_OR(hipEventCreateWithFlags(&c->u8_up_ev, hipEventDisableTiming), HVWS_EHIP);
-        if (c->u8_up_pending) {   // the previous pass's copy out of the slot
-            HIP_OR(hipEventSynchronize(c->u8_up_ev), HVWS_EHIP);
-            c->u8_up_pending = false;
-        }
-        HIP_OR(c->h_u8_in.ensure((uint64_t)nseg * 4), HVWS_ENOMEM);
-        memcpy(c->h_u8_in.p, state_in, (uint64_t)nseg * 4);
-        HIP_OR(hipMemcpyAsync(c->u8_in.p, c->h_u8_in.p, (uint64_t)nseg * 4, hipMemcpyHostToDevice, c->stream),
-               HVWS_EHIP);
-        HIP_OR(hipEventRecord(c->u8_up_ev, c->stream), HVWS_EHIP);
-        c->u8_up_pending = true;
-    }
-    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    HIP_OR(c->u8.words.ensure(cap * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->u8.flags.ensure_zeroed(cap * 4 + 16, c->stream), HVWS_ENOMEM);
+    HIP_OR(c->u8.tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
+    HIP_OR(c->u8.meta.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->u8.in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->u8.out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->u8.bad.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    if ((rc = c->u8.up.send(c->u8.in.p, c->stream, state_in, (uint64_t)nseg * 4)) != HVWS_OK) return rc;
+    HIP_OR(timed_begin(c), HVWS_EHIP);
     if (ntiles)
         HIP_OR(launch_tile_index(c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), 0, c->T().total.as<uint64_t>(),
-                                 c->u8_tiles.as<uint32_t>(), ntiles, U8_TILE, c->stream),
+                                 c->u8.tiles.as<uint32_t>(), ntiles, U8_TILE, c->stream),
                HVWS_EHIP);
     HIP_OR(launch_utf8(d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
                        c->T().f_keyrot.as<uint32_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(), cap,
-                       c->u8_tiles.as<uint32_t>(), ntiles, masked, c->u8_flags.as<uint32_t>(),
-                       c->u8_words.as<uint32_t>(), c->u8_meta.as<uint64_t>(), c->T().counts.as<uint64_t>(),
-                       c->T().bases.as<uint64_t>(), nseg, state_in ? c->u8_in.as<uint32_t>() : nullptr,
-                       c->u8_out.as<uint32_t>(), c->u8_bad.as<uint64_t>(), c->stream),
+                       c->u8.tiles.as<uint32_t>(), ntiles, masked, c->u8.flags.as<uint32_t>(),
+                       c->u8.words.as<uint32_t>(), c->u8.meta.as<uint64_t>(), c->T().counts.as<uint64_t>(),
+                       c->T().bases.as<uint64_t>(), nseg, state_in ? c->u8.in.as<uint32_t>() : nullptr,
+                       c->u8.out.as<uint32_t>(), c->u8.bad.as<uint64_t>(), c->stream),
            HVWS_EHIP);
-    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-    c->ev_build = true;
-    // Pipelined steps: the scan two steps on writes this table set and must
-    // wait for this pass as it waits for the set's unmask.
-    if (c->piped) {
-        HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
-        c->T().free_wait = c->T().free_ev;
-        c->T().free_pending = true;
-    }
-    c->have_u8 = true;
-    c->u8_nseg = nseg;
-    c->u8_gen = c->scan_gen;
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    HIP_OR(hold_tables(c), HVWS_EHIP);
+    c->u8.have = true;
+    c->u8.nseg = nseg;
+    c->u8.gen = c->scan_gen;
     return HVWS_OK;
 }
 
 int64_t hvws_utf8_count(hvws_ctx* c) {
-    if (!c || !c->have_u8 || check_ctx(c) != HVWS_OK) return -1;
-    uint64_t nrec = 0;
-    if (hipMemcpyAsync(&nrec, c->u8_meta.p, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_err(HVWS_EHIP, "hvws_utf8_count: reading the count failed");
-        return -1;
-    }
-    return (int64_t)nrec;
+    if (!c || !c->u8.have || check_ctx(c) != HVWS_OK) return -1;
+    return read_count(c, c->u8.meta.as<uint64_t>(), "hvws_utf8_count");
 }
 
 int hvws_get_utf8_words(hvws_ctx* c, uint32_t* out, uint64_t first, uint64_t n) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_u8) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->u8.have) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
     const int64_t have = hvws_utf8_count(c);
     if (have < 0) return HVWS_EHIP;
     const uint64_t nrec = (uint64_t)have;
     if (first > nrec || n > nrec - first) return set_err(HVWS_EINVAL, "word range out of bounds");
     if (n == 0) return HVWS_OK;
     if (!out) return set_err(HVWS_EINVAL, "null output");
-    HIP_OR(hipMemcpyAsync(out, c->u8_words.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    return read_rows(c, {{out, c->u8.words.as<uint32_t>() + first, n * 4}});
 }
 
 int hvws_get_utf8(hvws_ctx* c, uint32_t* state_out, uint64_t* bad) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_u8) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
-    const uint64_t nseg = c->u8_nseg;
-    if (state_out && nseg)
-        HIP_OR(hipMemcpyAsync(state_out, c->u8_out.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (bad && nseg) HIP_OR(hipMemcpyAsync(bad, c->u8_bad.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->u8.have) return set_err(HVWS_EINVAL, "no hvws_utf8 call yet");
+    const uint64_t nseg = c->u8.nseg;
+    return read_rows(c, {{state_out, c->u8.out.p, nseg * 4}, {bad, c->u8.bad.p, nseg * 8}});
 }
 
 uint64_t hvws_utf8_tile(void) { return U8_TILE; }
@@ -2738,9 +2846,7 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
                   const hvws_msg_state* state_in, const msg_prev* prev, bool rfc = false) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!c->have_scan) return set_err(HVWS_EINVAL, "hvws_messages without a preceding hvws_scan");
-    if (!d_rx || d_rx != c->rx || rx_len != c->rx_len)
-        return set_err(HVWS_EINVAL, "hvws_messages buffer differs from the scanned one");
+    if ((rc = behind_scan(c, "hvws_messages", d_rx, rx_len)) != HVWS_OK) return rc;
     if (!d_out || ((uintptr_t)d_out & 15u) != 0)
         return set_err(HVWS_EINVAL, "hvws_messages: d_out must be 16-byte aligned");
     {
@@ -2776,8 +2882,7 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     const bool rows = prev && nseg;   // without segments there is no carried row: the plain tables
     // a RUN step left no frame table: build it now (as hvws_unmask does)
     if (c->run_active && (rc = run_materialize(c)) != HVWS_OK) return rc;
-    // c->nfr: the record count, or its bound while the count is on the device
-    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
+    const uint64_t cap = record_bound(c);
     const uint64_t ncap = rows ? cap + vn : cap;   // rows, and the bound of the pieces
     // the output cannot exceed the batch and what is carried
     const uint64_t need = carried > UINT64_MAX - rx_len ? UINT64_MAX : rx_len + carried;
@@ -2785,133 +2890,109 @@ int messages_pass(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int masked,
     const int geom = msg_variant(need, cap);
     const uint64_t tile = msg_gather_tile(geom);
     uint64_t ntiles = (bound + tile - 1) / tile;
-    HIP_OR(c->mg_scan.ensure(msg_scratch_bytes(ncap)), HVWS_ENOMEM);
-    HIP_OR(c->mg_off.ensure(ncap * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
-    HIP_OR(c->mg_msgs.ensure((ncap + 1) * sizeof(dmsg)), HVWS_ENOMEM);
-    HIP_OR(c->mg_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg.scan.ensure(msg_scratch_bytes(ncap)), HVWS_ENOMEM);
+    HIP_OR(c->mg.off.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg.tiles.ensure((ntiles + 8) * 4), HVWS_ENOMEM);
+    HIP_OR(c->mg.msgs.ensure((ncap + 1) * sizeof(dmsg)), HVWS_ENOMEM);
+    HIP_OR(c->mg.first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg.count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     // state_in, then (joined) prev_off
-    HIP_OR(c->mg_in.ensure(vn * (sizeof(dmsg_state) + 8) + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_out.ensure((uint64_t)nseg * (rfc ? sizeof(drfc_state) : sizeof(dmsg_state)) + 16), HVWS_ENOMEM);
-    HIP_OR(c->mg_meta.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->mg.in.ensure(vn * (sizeof(dmsg_state) + 8) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg.out.ensure((uint64_t)nseg * (rfc ? sizeof(drfc_state) : sizeof(dmsg_state)) + 16), HVWS_ENOMEM);
+    HIP_OR(c->mg.meta.ensure(64), HVWS_ENOMEM);
     if (rows) {
-        HIP_OR(c->mj_len.ensure(ncap * 8 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mj_src.ensure(ncap * 8 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mj_key.ensure(ncap * 4 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mj_info.ensure(ncap * 4 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mj_prow.ensure((ncap + 1) * 8), HVWS_ENOMEM);
-        HIP_OR(c->mj_carry.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.row_len.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.row_src.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.row_key.ensure(ncap * 4 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.row_info.ensure(ncap * 4 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.prow.ensure((ncap + 1) * 8), HVWS_ENOMEM);
+        HIP_OR(c->mg.carry.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     }
     if (rows && rfc) {
-        HIP_OR(c->mr_cls.ensure(msg_cls_bytes(cap)), HVWS_ENOMEM);
-        HIP_OR(c->mr_rec.ensure(ncap * 8 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mr_vbase.ensure(vn * 8 + 16), HVWS_ENOMEM);
-        HIP_OR(c->mr_vcnt.ensure(vn * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.cls.ensure(msg_cls_bytes(cap)), HVWS_ENOMEM);
+        HIP_OR(c->mg.rec.ensure(ncap * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.vbase.ensure(vn * 8 + 16), HVWS_ENOMEM);
+        HIP_OR(c->mg.vcnt.ensure(vn * 8 + 16), HVWS_ENOMEM);
     }
-    c->have_msg = false;   // the tables are being rewritten
-    c->have_join = false;
-    c->have_rfc = false;
-    c->have_rep = false;   // ... which a reply table indexes
+    c->mg.have = false;   // the tables are being rewritten
+    c->mg.joined = false;
+    c->mg.rfc = false;
+    c->rp.have = false;   // ... which a reply table indexes
     const bool with_off = rows && carried;   // prev_off rides behind the states in the same slot
-    if (state_in && nseg) {
-        const uint64_t sbytes = vn * sizeof(dmsg_state);
-        const uint64_t bytes = sbytes + (with_off ? vn * 8 : 0);
-        if (!c->mg_up_ev) HIP_OR(hipEventCreateWithFlags(&c->mg_up_ev, hipEventDisableTiming), HVWS_EHIP);
-        if (c->mg_up_pending) {   // the previous pass's copy out of the slot
-            HIP_OR(hipEventSynchronize(c->mg_up_ev), HVWS_EHIP);
-            c->mg_up_pending = false;
-        }
-        HIP_OR(c->h_mg_in.ensure(bytes), HVWS_ENOMEM);
-        memcpy(c->h_mg_in.p, state_in, sbytes);
-        if (with_off) memcpy((uint8_t*)c->h_mg_in.p + sbytes, prev->off, vn * 8);
-        HIP_OR(hipMemcpyAsync(c->mg_in.p, c->h_mg_in.p, bytes, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
-        HIP_OR(hipEventRecord(c->mg_up_ev, c->stream), HVWS_EHIP);
-        c->mg_up_pending = true;
-    }
-    const msg_rows mr{c->mj_len.as<uint64_t>(), c->mj_src.as<uint64_t>(), c->mj_key.as<uint32_t>(),
-                      c->mj_info.as<uint32_t>(), c->mj_prow.as<uint64_t>()};
-    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    if ((rc = c->mg.up.send(c->mg.in.p, c->stream, state_in, vn * sizeof(dmsg_state), with_off ? prev->off : nullptr,
+                            with_off ? vn * 8 : 0)) != HVWS_OK)
+        return rc;
+    const msg_rows mr{c->mg.row_len.as<uint64_t>(), c->mg.row_src.as<uint64_t>(), c->mg.row_key.as<uint32_t>(),
+                      c->mg.row_info.as<uint32_t>(), c->mg.prow.as<uint64_t>()};
+    HIP_OR(timed_begin(c), HVWS_EHIP);
     if (rows) {
         const dframes fr{nullptr, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(), nullptr, nullptr,
                          c->T().f_keyrot.as<uint32_t>(), c->T().f_info.as<uint32_t>(), cap};
         const uint64_t* d_prev_off =
-            with_off ? reinterpret_cast<const uint64_t*>((uint8_t*)c->mg_in.p + vn * sizeof(dmsg_state)) : nullptr;
+            with_off ? reinterpret_cast<const uint64_t*>((uint8_t*)c->mg.in.p + vn * sizeof(dmsg_state)) : nullptr;
         if (rfc) {
-            const rfc_rows rr{c->mr_rec.as<uint64_t>(), c->mr_vbase.as<uint64_t>(), c->mr_vcnt.as<uint64_t>()};
+            const rfc_rows rr{c->mg.rec.as<uint64_t>(), c->mg.vbase.as<uint64_t>(), c->mg.vcnt.as<uint64_t>()};
             HIP_OR(launch_msg_table_rfc(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().bases.as<uint64_t>(), nseg,
-                                        state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p,
-                                        c->mr_cls.p, mr, rr, c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(),
-                                        c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
-                                        c->mg_out.as<drfc_state>(), c->mg_meta.as<uint64_t>(), c->stream),
+                                        state_in ? c->mg.in.as<dmsg_state>() : nullptr, d_prev_off, c->mg.scan.p,
+                                        c->mg.cls.p, mr, rr, c->mg.off.as<uint64_t>(), c->mg.msgs.as<dmsg>(),
+                                        c->mg.first.as<uint64_t>(), c->mg.count.as<uint64_t>(),
+                                        c->mg.out.as<drfc_state>(), c->mg.meta.as<uint64_t>(), c->stream),
                    HVWS_EHIP);
         } else {
             HIP_OR(launch_msg_table_joined(fr, masked, c->T().total.as<uint64_t>(), cap, c->T().counts.as<uint64_t>(),
                                            c->T().bases.as<uint64_t>(), nseg,
-                                           state_in ? c->mg_in.as<dmsg_state>() : nullptr, d_prev_off, c->mg_scan.p,
-                                           mr, c->mg_off.as<uint64_t>(), c->mg_msgs.as<dmsg>(),
-                                           c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
-                                           c->mg_out.as<dmsg_state>(), c->mj_carry.as<uint64_t>(),
-                                           c->mg_meta.as<uint64_t>(), c->stream),
+                                           state_in ? c->mg.in.as<dmsg_state>() : nullptr, d_prev_off, c->mg.scan.p,
+                                           mr, c->mg.off.as<uint64_t>(), c->mg.msgs.as<dmsg>(),
+                                           c->mg.first.as<uint64_t>(), c->mg.count.as<uint64_t>(),
+                                           c->mg.out.as<dmsg_state>(), c->mg.carry.as<uint64_t>(),
+                                           c->mg.meta.as<uint64_t>(), c->stream),
                    HVWS_EHIP);
         }
     } else {
         HIP_OR(launch_msg_table(c->T().f_len.as<uint64_t>(), c->T().f_info.as<uint32_t>(), c->T().total.as<uint64_t>(),
                                 cap, c->T().counts.as<uint64_t>(), c->T().bases.as<uint64_t>(), nseg,
-                                state_in ? c->mg_in.as<dmsg_state>() : nullptr, c->mg_scan.p, c->mg_off.as<uint64_t>(),
-                                c->mg_msgs.as<dmsg>(), c->mg_first.as<uint64_t>(), c->mg_count.as<uint64_t>(),
-                                c->mg_out.as<dmsg_state>(), c->mg_meta.as<uint64_t>(), c->stream),
+                                state_in ? c->mg.in.as<dmsg_state>() : nullptr, c->mg.scan.p, c->mg.off.as<uint64_t>(),
+                                c->mg.msgs.as<dmsg>(), c->mg.first.as<uint64_t>(), c->mg.count.as<uint64_t>(),
+                                c->mg.out.as<dmsg_state>(), c->mg.meta.as<uint64_t>(), c->stream),
                HVWS_EHIP);
     }
-    // Pipelined steps: the scan two steps on writes this table set and must
-    // wait for this pass as it waits for the set's unmask.
-    auto free_event = [&]() -> int {
-        if (c->piped) {
-            HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
-            c->T().free_wait = c->T().free_ev;
-            c->T().free_pending = true;
-        }
-        return HVWS_OK;
-    };
     bool fits = true;
     if (out_cap < need) {   // the one wait: does the payload fit?
         uint64_t total = 0;
-        HIP_OR(hipMemcpyAsync(&total, c->mg_meta.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-        HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+        HIP_OR(read_word(c, c->mg.meta.as<uint64_t>() + 1, &total), HVWS_EHIP);
         fits = total <= out_cap;
         ntiles = (std::min(total, out_cap) + tile - 1) / tile;
     }
     if (fits) {
         // the tile index over the output: by records, or by rows (meta[0] counts either)
         if (ntiles)
-            HIP_OR(launch_tile_index(c->mg_off.as<uint64_t>(), rows ? mr.len : c->T().f_len.as<uint64_t>(), 0,
-                                     c->mg_meta.as<uint64_t>(), c->mg_tiles.as<uint32_t>(), ntiles, tile, c->stream),
+            HIP_OR(launch_tile_index(c->mg.off.as<uint64_t>(), rows ? mr.len : c->T().f_len.as<uint64_t>(), 0,
+                                     c->mg.meta.as<uint64_t>(), c->mg.tiles.as<uint32_t>(), ntiles, tile, c->stream),
                    HVWS_EHIP);
         if (rows)
             HIP_OR(launch_msg_gather_joined(geom, d_rx, rx_len, prev->d, prev->d ? prev->len : 0, mr,
-                                            c->mg_off.as<uint64_t>(), c->mg_tiles.as<uint32_t>(), ntiles,
-                                            c->mg_meta.as<uint64_t>(), masked, d_out, out_cap, c->stream),
+                                            c->mg.off.as<uint64_t>(), c->mg.tiles.as<uint32_t>(), ntiles,
+                                            c->mg.meta.as<uint64_t>(), masked, d_out, out_cap, c->stream),
                    HVWS_EHIP);
         else
             HIP_OR(launch_msg_gather(geom, d_rx, rx_len, c->T().f_off.as<uint64_t>(), c->T().f_len.as<uint64_t>(),
-                                     c->T().f_keyrot.as<uint32_t>(), c->mg_off.as<uint64_t>(),
-                                     c->mg_tiles.as<uint32_t>(), ntiles, c->mg_meta.as<uint64_t>(), masked, d_out,
+                                     c->T().f_keyrot.as<uint32_t>(), c->mg.off.as<uint64_t>(),
+                                     c->mg.tiles.as<uint32_t>(), ntiles, c->mg.meta.as<uint64_t>(), masked, d_out,
                                      out_cap, c->stream),
                    HVWS_EHIP);
     }
-    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-    c->ev_build = true;
-    if ((rc = free_event()) != HVWS_OK) return rc;
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    HIP_OR(hold_tables(c), HVWS_EHIP);   // even when the payload does not fit: the table pass ran
     if (!fits) return set_err(HVWS_EINVAL, "hvws_messages: the payload does not fit out_cap");
-    c->have_msg = true;
-    c->have_join = prev != nullptr && !rfc;
-    c->have_rfc = rfc;
-    c->mg_nseg = nseg;
-    c->mg_cap = ncap;
-    c->mg_gen = c->scan_gen;
-    ++c->msg_seq;
-    c->mg_dout = d_out;
-    c->mg_out_cap = out_cap;
+    c->mg.have = true;
+    c->mg.joined = prev != nullptr && !rfc;
+    c->mg.rfc = rfc;
+    c->mg.nseg = nseg;
+    c->mg.cap = ncap;
+    c->mg.gen = c->scan_gen;
+    ++c->mg.seq;
+    c->mg.dout = d_out;
+    c->mg.out_cap = out_cap;
     return HVWS_OK;
 }
 }  // namespace
@@ -2936,48 +3017,37 @@ int hvws_messages_rfc(hvws_ctx* c, const uint8_t* d_rx, uint64_t rx_len, int mas
     if (rc) return rc;
     const uint32_t nseg = c->nseg;
     if (state_in) {
-        c->rf_st.resize(2ull * nseg);
-        c->rf_off.resize(2ull * nseg);
+        c->mg.rf_st.resize(2ull * nseg);
+        c->mg.rf_off.resize(2ull * nseg);
         for (uint32_t s = 0; s < nseg; ++s) {
-            c->rf_st[2ull * s] = state_in[s].data;
-            c->rf_st[2ull * s + 1] = state_in[s].ctl;
-            c->rf_off[2ull * s] = state_in[s].data_off;
-            c->rf_off[2ull * s + 1] = state_in[s].ctl_off;
+            c->mg.rf_st[2ull * s] = state_in[s].data;
+            c->mg.rf_st[2ull * s + 1] = state_in[s].ctl;
+            c->mg.rf_off[2ull * s] = state_in[s].data_off;
+            c->mg.rf_off[2ull * s + 1] = state_in[s].ctl_off;
         }
     }
-    const msg_prev prev{d_prev, d_prev ? prev_len : 0, state_in ? c->rf_off.data() : nullptr};
-    return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in ? c->rf_st.data() : nullptr, &prev, true);
+    const msg_prev prev{d_prev, d_prev ? prev_len : 0, state_in ? c->mg.rf_off.data() : nullptr};
+    return messages_pass(c, d_rx, rx_len, masked, d_out, out_cap, state_in ? c->mg.rf_st.data() : nullptr, &prev, true);
 }
 
 int hvws_get_rfc_state(hvws_ctx* c, hvws_rfc_state* out) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_msg || !c->have_rfc) return set_err(HVWS_EINVAL, "no hvws_messages_rfc call yet");
-    const uint64_t nseg = c->mg_nseg;
-    if (out && nseg)
-        HIP_OR(hipMemcpyAsync(out, c->mg_out.p, nseg * sizeof(drfc_state), hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->mg.have || !c->mg.rfc) return set_err(HVWS_EINVAL, "no hvws_messages_rfc call yet");
+    return read_rows(c, {{out, c->mg.out.p, c->mg.nseg * sizeof(drfc_state)}});
 }
 
 int hvws_get_msg_carry(hvws_ctx* c, uint64_t* off) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_msg || !c->have_join) return set_err(HVWS_EINVAL, "no hvws_messages_joined call yet");
-    const uint64_t nseg = c->mg_nseg;
-    if (off && nseg) HIP_OR(hipMemcpyAsync(off, c->mj_carry.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->mg.have || !c->mg.joined) return set_err(HVWS_EINVAL, "no hvws_messages_joined call yet");
+    return read_rows(c, {{off, c->mg.carry.p, (uint64_t)c->mg.nseg * 8}});
 }
 
 namespace {
 // meta word i of the last hvws_messages (1: payload bytes, 2: pieces); waits
 int msg_meta(hvws_ctx* c, int i, uint64_t* v) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
-    HIP_OR(hipMemcpyAsync(v, c->mg_meta.as<uint64_t>() + i, 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->mg.have) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    HIP_OR(read_word(c, c->mg.meta.as<uint64_t>() + i, v), HVWS_EHIP);
     return HVWS_OK;
 }
 }  // namespace
@@ -3000,38 +3070,26 @@ int hvws_get_messages(hvws_ctx* c, hvws_msg* out, uint64_t first, uint64_t n) {
     if (first > have || n > have - first) return set_err(HVWS_EINVAL, "piece range out of bounds");
     if (n == 0) return HVWS_OK;
     if (!out) return set_err(HVWS_EINVAL, "null output");
-    HIP_OR(hipMemcpyAsync(out, c->mg_msgs.as<dmsg>() + first, n * sizeof(dmsg), hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    return read_rows(c, {{out, c->mg.msgs.as<dmsg>() + first, n * sizeof(dmsg)}});
 }
 
 int hvws_get_segment_messages(hvws_ctx* c, uint64_t* first, uint64_t* count) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
-    const uint64_t nseg = c->mg_nseg;
-    if (first && nseg) HIP_OR(hipMemcpyAsync(first, c->mg_first.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (count && nseg) HIP_OR(hipMemcpyAsync(count, c->mg_count.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->mg.have) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    const uint64_t nseg = c->mg.nseg;
+    return read_rows(c, {{first, c->mg.first.p, nseg * 8}, {count, c->mg.count.p, nseg * 8}});
 }
 
 int hvws_get_msg_state(hvws_ctx* c, hvws_msg_state* out) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_msg) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
-    if (c->have_rfc) return set_err(HVWS_EINVAL, "hvws_get_msg_state after hvws_messages_rfc: hvws_get_rfc_state");
-    const uint64_t nseg = c->mg_nseg;
-    if (out && nseg)
-        HIP_OR(hipMemcpyAsync(out, c->mg_out.p, nseg * sizeof(dmsg_state), hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->mg.have) return set_err(HVWS_EINVAL, "no hvws_messages call yet");
+    if (c->mg.rfc) return set_err(HVWS_EINVAL, "hvws_get_msg_state after hvws_messages_rfc: hvws_get_rfc_state");
+    return read_rows(c, {{out, c->mg.out.p, c->mg.nseg * sizeof(dmsg_state)}});
 }
 
 const hvws_msg* hvws_messages_device(hvws_ctx* c) {
-    if (!c || !c->have_msg) return nullptr;
-    return c->mg_msgs.as<hvws_msg>();
+    if (!c || !c->mg.have) return nullptr;
+    return c->mg.msgs.as<hvws_msg>();
 }
 
 uint64_t hvws_msg_tile(void) { return MSG_TILE; }
@@ -3094,20 +3152,14 @@ int hvws_get_frames(hvws_ctx* c, hvws_frame* out, uint64_t first, uint64_t n) {
     std::vector<int64_t> hdr(n);
     std::vector<uint64_t> off(n), len(n), length(n);
     std::vector<uint32_t> key(n), info(n);
-    HIP_OR(hipMemcpyAsync(hdr.data(), c->T().f_hdr.as<int64_t>() + first, n * 8, hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipMemcpyAsync(off.data(), c->T().f_off.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipMemcpyAsync(len.data(), c->T().f_len.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipMemcpyAsync(length.data(), c->T().f_length.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost,
-                          c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipMemcpyAsync(key.data(), c->T().f_key.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipMemcpyAsync(info.data(), c->T().f_info.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost, c->stream),
-           HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
+    const tset& t = c->T();
+    if ((rc = read_rows(c, {{hdr.data(), t.f_hdr.as<int64_t>() + first, n * 8},
+                            {off.data(), t.f_off.as<uint64_t>() + first, n * 8},
+                            {len.data(), t.f_len.as<uint64_t>() + first, n * 8},
+                            {length.data(), t.f_length.as<uint64_t>() + first, n * 8},
+                            {key.data(), t.f_key.as<uint32_t>() + first, n * 4},
+                            {info.data(), t.f_info.as<uint32_t>() + first, n * 4}})) != HVWS_OK)
+        return rc;
     for (uint64_t i = 0; i < n; ++i) {
         out[i].hdr_off = hdr[i];
         out[i].pay_off = off[i];
@@ -3415,26 +3467,26 @@ int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8
     if (!d_out || !d_pay_off || !d_len || !d_flags) return set_err(HVWS_EINVAL, "build_frames: null table");
     if (n >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "build_frames: %llu frames (max 2^32-2)", (unsigned long long)n);
     const uint64_t nb = (n + 1023) / 1024;
-    HIP_OR(c->tx_size.ensure(n * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->tx_scan.ensure((4 * nb + 64) * 8), HVWS_ENOMEM);
-    HIP_OR(c->tx_stat.ensure(64), HVWS_ENOMEM);
-    HIP_OR(c->h_tx.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->tx.size.ensure(n * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->tx.scan.ensure((4 * nb + 64) * 8), HVWS_ENOMEM);
+    HIP_OR(c->tx.stat.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->tx.h.ensure(64), HVWS_ENOMEM);
     uint64_t* off = d_out_off;
     if (!off) {
-        HIP_OR(c->tx_off.ensure(n * 8 + 8), HVWS_ENOMEM);
-        off = c->tx_off.as<uint64_t>();
+        HIP_OR(c->tx.off.ensure(n * 8 + 8), HVWS_ENOMEM);
+        off = c->tx.off.as<uint64_t>();
     }
     // [0] total bytes, [1] payload ranges out of bounds, [2] frames breaking
     // the uniform layout, [3..5] pay_off[0], its step, len[0] (k_tx_check)
-    uint64_t* stat = c->tx_stat.as<uint64_t>();
+    uint64_t* stat = c->tx.stat.as<uint64_t>();
     HIP_OR(hipMemsetAsync(stat, 0, 64, c->stream), HVWS_EHIP);
-    HIP_OR(launch_frame_sizes(d_flags, d_len, n, c->tx_size.as<uint64_t>(), c->stream), HVWS_EHIP);
-    HIP_OR(launch_exclusive_scan(c->tx_size.as<uint64_t>(), off, n, c->tx_scan.as<uint64_t>(), stat, c->stream),
+    HIP_OR(launch_frame_sizes(d_flags, d_len, n, c->tx.size.as<uint64_t>(), c->stream), HVWS_EHIP);
+    HIP_OR(launch_exclusive_scan(c->tx.size.as<uint64_t>(), off, n, c->tx.scan.as<uint64_t>(), stat, c->stream),
            HVWS_EHIP);
-    HIP_OR(launch_tx_check(d_pay_off, d_len, d_flags, d_mask, c->tx_size.as<uint64_t>(), n, payload_len, stat,
+    HIP_OR(launch_tx_check(d_pay_off, d_len, d_flags, d_mask, c->tx.size.as<uint64_t>(), n, payload_len, stat,
                            c->stream),
            HVWS_EHIP);
-    uint64_t* h = c->h_tx.as<uint64_t>();
+    uint64_t* h = c->tx.h.as<uint64_t>();
     HIP_OR(hipMemcpyAsync(h, stat, 48, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
     HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
     if (h[1]) return set_err(HVWS_EINVAL, "build_frames: %llu frames read outside the payload buffer or lack a mask",
@@ -3445,7 +3497,7 @@ int hvws_build_frames(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint8
         return set_err(HVWS_EINVAL, "build_frames: output needs %llu bytes, capacity %llu", (unsigned long long)total,
                        (unsigned long long)out_cap);
     return tx_build_checked(c, d_out, total, d_payload, payload_len, d_pay_off, d_len, d_flags, d_mask, off,
-                            c->tx_size.as<uint64_t>(), n, h + 2, nullptr);
+                            c->tx.size.as<uint64_t>(), n, h + 2, nullptr);
 }
 
 namespace {
@@ -3463,7 +3515,7 @@ int tx_build_checked(hvws_ctx* c, uint8_t* d_out, uint64_t total, const uint8_t*
     // takes k_build (round 4: it reached or beat the same-offset kernel
     // k_build_id, which is gone, profiles/r4v_raw)
     const int v = tx_variant(total, n);
-    c->tx_variant = v;
+    c->tx.variant = v;
     // each tile's source span first (round 4: records-first tiles lost, and
     // their switch went in round 6)
     const bool spans_ok = true;
@@ -3480,24 +3532,23 @@ int tx_build_checked(hvws_ctx* c, uint8_t* d_out, uint64_t total, const uint8_t*
     // layout, 21.3 against 20.2 ms at c3, profiles/r5b_raw)
     const bool uniform = uni_ok && v == 5 && uh[0] == 0 && total % n == 0 && (n == 1 || uh[2] >= uh[3]);
     const uint64_t uni[4] = {uniform ? total / n : 0, uniform ? total / n - uh[3] : 0, uh[1], uh[2]};
-    c->tx_uniform = uniform;
+    c->tx.uniform = uniform;
     if (!uniform) {
-        HIP_OR(c->tx_tiles.ensure((ntiles + 2) * 4), HVWS_ENOMEM);
-        if (spans_ok) HIP_OR(c->tx_span.ensure(ntiles * 16 + 16), HVWS_ENOMEM);
+        HIP_OR(c->tx.tiles.ensure((ntiles + 2) * 4), HVWS_ENOMEM);
+        if (spans_ok) HIP_OR(c->tx.span.ensure(ntiles * 16 + 16), HVWS_ENOMEM);
     }
     // the timed device work (hvws_last_kernel_ms): tile index, spans, build
-    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
-    uint64_t* span = spans_ok && !uniform ? c->tx_span.as<uint64_t>() : nullptr;
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    uint64_t* span = spans_ok && !uniform ? c->tx.span.as<uint64_t>() : nullptr;
     if (pre) HIP_OR((*pre)(), HVWS_EHIP);
     if (!uniform)
-        HIP_OR(launch_tx_index(off, size, d_pay_off, d_len, d_flags, n, ntiles, tile, c->tx_tiles.as<uint32_t>(), span,
+        HIP_OR(launch_tx_index(off, size, d_pay_off, d_len, d_flags, n, ntiles, tile, c->tx.tiles.as<uint32_t>(), span,
                                c->stream),
                HVWS_EHIP);
     HIP_OR(launch_build(d_out, total, d_payload, payload_len, d_pay_off, d_len, d_flags, d_mask, off, size,
-                        c->tx_tiles.as<uint32_t>(), span, n, v, c->stream, uni),
+                        c->tx.tiles.as<uint32_t>(), span, n, v, c->stream, uni),
            HVWS_EHIP);
-    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-    c->ev_build = true;
+    HIP_OR(timed_end(c), HVWS_EHIP);
     return HVWS_OK;
 }
 }  // namespace
@@ -3532,18 +3583,18 @@ int hvws_send_messages(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint
     if (n >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "send_messages: %llu messages (max 2^32-2)", (unsigned long long)n);
     const uint64_t F = fragment ? fragment : 0xFFFFu;   // WebSocketChannel.cpp:6
     const dtxmsg* msgs = reinterpret_cast<const dtxmsg*>(d_msgs);
-    HIP_OR(c->sd_scan.ensure(send_scratch_bytes(n)), HVWS_ENOMEM);
-    HIP_OR(c->sd_first.ensure(n * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->sd_meta.ensure(64), HVWS_ENOMEM);
-    HIP_OR(c->h_tx.ensure(64), HVWS_ENOMEM);
-    uint64_t* meta = c->sd_meta.as<uint64_t>();
+    HIP_OR(c->sd.scan.ensure(send_scratch_bytes(n)), HVWS_ENOMEM);
+    HIP_OR(c->sd.first.ensure(n * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->sd.meta.ensure(64), HVWS_ENOMEM);
+    HIP_OR(c->tx.h.ensure(64), HVWS_ENOMEM);
+    uint64_t* meta = c->sd.meta.as<uint64_t>();
     HIP_OR(hipMemsetAsync(meta, 0, 64, c->stream), HVWS_EHIP);
-    HIP_OR(launch_send_table(msgs, n, d_n, payload_len, F, masked, c->sd_scan.p, c->sd_first.as<uint64_t>(), d_msg_off,
+    HIP_OR(launch_send_table(msgs, n, d_n, payload_len, F, masked, c->sd.scan.p, c->sd.first.as<uint64_t>(), d_msg_off,
                              meta, c->stream),
            HVWS_EHIP);
     // [0] frames, [1] bytes, [2] bad messages, [3] effective count, [4] messages
     // breaking the uniform layout, [5..7] off[0], its step, len[0]
-    uint64_t* h = c->h_tx.as<uint64_t>();
+    uint64_t* h = c->tx.h.as<uint64_t>();
     HIP_OR(hipMemcpyAsync(h, meta, 64, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
     HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
     if (h[2])
@@ -3558,28 +3609,27 @@ int hvws_send_messages(hvws_ctx* c, uint8_t* d_out, uint64_t out_cap, const uint
                        (unsigned long long)out_cap);
     if (out_frames) *out_frames = nfr;
     if (nfr == 0) {   // *d_n was 0: nothing to build; the timed region is empty
-        HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
-        HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-        c->ev_build = true;
+        HIP_OR(timed_begin(c), HVWS_EHIP);
+        HIP_OR(timed_end(c), HVWS_EHIP);
         return HVWS_OK;
     }
-    HIP_OR(c->sd_poff.ensure(nfr * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->sd_len.ensure(nfr * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->sd_flags.ensure(nfr + 8), HVWS_ENOMEM);
-    HIP_OR(c->sd_mask.ensure(nfr * 4 + 8), HVWS_ENOMEM);
-    HIP_OR(c->tx_off.ensure(nfr * 8 + 8), HVWS_ENOMEM);
-    HIP_OR(c->tx_size.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd.poff.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd.len.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd.flags.ensure(nfr + 8), HVWS_ENOMEM);
+    HIP_OR(c->sd.mask.ensure(nfr * 4 + 8), HVWS_ENOMEM);
+    HIP_OR(c->tx.off.ensure(nfr * 8 + 8), HVWS_ENOMEM);
+    HIP_OR(c->tx.size.ensure(nfr * 8 + 8), HVWS_ENOMEM);
     const std::function<hipError_t()> expand = [&]() {
-        return launch_send_expand(msgs, c->sd_scan.p, c->sd_first.as<uint64_t>(), meta, nfr, F, masked,
-                                  c->sd_poff.as<uint64_t>(), c->sd_len.as<uint64_t>(), c->sd_flags.as<uint8_t>(),
-                                  c->sd_mask.as<uint32_t>(), c->tx_off.as<uint64_t>(), c->tx_size.as<uint64_t>(),
+        return launch_send_expand(msgs, c->sd.scan.p, c->sd.first.as<uint64_t>(), meta, nfr, F, masked,
+                                  c->sd.poff.as<uint64_t>(), c->sd.len.as<uint64_t>(), c->sd.flags.as<uint8_t>(),
+                                  c->sd.mask.as<uint32_t>(), c->tx.off.as<uint64_t>(), c->tx.size.as<uint64_t>(),
                                   c->stream);
     };
     // the frames form a uniform layout when the messages do, one frame each
     const uint64_t uh[4] = {h[4] + (nfr != h[3] ? 1u : 0u), h[5], h[6], h[7]};
-    return tx_build_checked(c, d_out, total, d_payload, payload_len, c->sd_poff.as<uint64_t>(),
-                            c->sd_len.as<uint64_t>(), c->sd_flags.as<uint8_t>(), c->sd_mask.as<uint32_t>(),
-                            c->tx_off.as<uint64_t>(), c->tx_size.as<uint64_t>(), nfr, uh, &expand);
+    return tx_build_checked(c, d_out, total, d_payload, payload_len, c->sd.poff.as<uint64_t>(),
+                            c->sd.len.as<uint64_t>(), c->sd.flags.as<uint8_t>(), c->sd.mask.as<uint32_t>(),
+                            c->tx.off.as<uint64_t>(), c->tx.size.as<uint64_t>(), nfr, uh, &expand);
 }
 
 // The server's onMessage dispatch over the last hvws_messages' pieces
@@ -3588,44 +3638,33 @@ namespace {
 int replies_pass(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in, bool checked) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!c->have_msg) return set_err(HVWS_EINVAL, "hvws_replies without a preceding hvws_messages");
-    if (checked && (!c->have_rfc || !c->have_chk || c->ck_msg != c->msg_seq))
+    if (!c->mg.have) return set_err(HVWS_EINVAL, "hvws_replies without a preceding hvws_messages");
+    if (checked && (!c->mg.rfc || !c->ck.have || c->ck.msg != c->mg.seq))
         return set_err(HVWS_EINVAL, "hvws_replies_checked without an hvws_check of the last hvws_messages_rfc");
     if (policy & ~(uint32_t)(HVWS_R_PONG | HVWS_R_CLOSE | HVWS_R_ECHO))
         return set_err(HVWS_EINVAL, "hvws_replies: unknown policy bits");
-    const uint32_t nseg = c->mg_nseg;
-    const uint64_t cap = c->mg_cap;
-    HIP_OR(c->rp_scan.ensure(rep_scratch_words(cap) * 8), HVWS_ENOMEM);
-    HIP_OR(c->rp_limit.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->rp_msgs.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
-    HIP_OR(c->rp_piece.ensure((cap + 1) * 8), HVWS_ENOMEM);
-    HIP_OR(c->rp_first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->rp_count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->rp_flags.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
-    HIP_OR(c->rp_closed.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
-    c->have_rep = false;   // the tables are being rewritten
-    if (closed_in && nseg) {
-        if (!c->rp_up_ev) HIP_OR(hipEventCreateWithFlags(&c->rp_up_ev, hipEventDisableTiming), HVWS_EHIP);
-        if (c->rp_up_pending) {   // the previous call's copy out of the slot
-            HIP_OR(hipEventSynchronize(c->rp_up_ev), HVWS_EHIP);
-            c->rp_up_pending = false;
-        }
-        HIP_OR(c->h_rp_in.ensure(nseg), HVWS_ENOMEM);
-        memcpy(c->h_rp_in.p, closed_in, nseg);
-        HIP_OR(hipMemcpyAsync(c->rp_closed.p, c->h_rp_in.p, nseg, hipMemcpyHostToDevice, c->stream), HVWS_EHIP);
-        HIP_OR(hipEventRecord(c->rp_up_ev, c->stream), HVWS_EHIP);
-        c->rp_up_pending = true;
-    }
-    HIP_OR(launch_replies(c->mg_msgs.as<dmsg>(), c->mg_meta.as<uint64_t>(), cap, c->mg_first.as<uint64_t>(),
-                          c->mg_count.as<uint64_t>(), nseg, policy, closed_in ? c->rp_closed.as<uint8_t>() : nullptr,
-                          c->rp_limit.as<uint64_t>(), c->rp_scan.as<uint64_t>(), c->rp_msgs.as<dtxmsg>(),
-                          c->rp_piece.as<uint64_t>(), c->rp_first.as<uint64_t>(), c->rp_count.as<uint64_t>(),
-                          c->rp_flags.as<uint8_t>(), c->have_rfc, c->stream,
-                          checked ? c->ck_fail.as<uint64_t>() : nullptr),
+    const uint32_t nseg = c->mg.nseg;
+    const uint64_t cap = c->mg.cap;
+    HIP_OR(c->rp.scan.ensure(rep_scratch_words(cap) * 8), HVWS_ENOMEM);
+    HIP_OR(c->rp.limit.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp.msgs.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(c->rp.piece.ensure((cap + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(c->rp.first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp.count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp.flags.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
+    HIP_OR(c->rp.closed.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
+    c->rp.have = false;   // the tables are being rewritten
+    if ((rc = c->rp.up.send(c->rp.closed.p, c->stream, closed_in, nseg)) != HVWS_OK) return rc;
+    HIP_OR(launch_replies(c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), cap, c->mg.first.as<uint64_t>(),
+                          c->mg.count.as<uint64_t>(), nseg, policy, closed_in ? c->rp.closed.as<uint8_t>() : nullptr,
+                          c->rp.limit.as<uint64_t>(), c->rp.scan.as<uint64_t>(), c->rp.msgs.as<dtxmsg>(),
+                          c->rp.piece.as<uint64_t>(), c->rp.first.as<uint64_t>(), c->rp.count.as<uint64_t>(),
+                          c->rp.flags.as<uint8_t>(), c->mg.rfc, c->stream,
+                          checked ? c->ck.fail.as<uint64_t>() : nullptr),
            HVWS_EHIP);
-    c->have_rep = true;
-    c->rp_nseg = nseg;
-    c->rp_cap = cap;
+    c->rp.have = true;
+    c->rp.nseg = nseg;
+    c->rp.cap = cap;
     return HVWS_OK;
 }
 }  // namespace
@@ -3650,108 +3689,78 @@ static_assert(CK_HEADER == HVWS_C_HEADER && CK_SEQUENCE == HVWS_C_SEQUENCE && CK
 int hvws_check(hvws_ctx* c, uint32_t classes, uint64_t max_message, const uint32_t* state_in) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!c->have_msg || !c->have_rfc) return set_err(HVWS_EINVAL, "hvws_check without a preceding hvws_messages_rfc");
-    if (c->mg_gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_check: a scan has run since hvws_messages_rfc");
+    if (!c->mg.have || !c->mg.rfc) return set_err(HVWS_EINVAL, "hvws_check without a preceding hvws_messages_rfc");
+    if (c->mg.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_check: a scan has run since hvws_messages_rfc");
     if (classes & ~(uint32_t)HVWS_C_ALL) return set_err(HVWS_EINVAL, "hvws_check: unknown class bits");
-    const uint32_t nseg = c->mg_nseg;
-    if ((classes & HVWS_C_TEXT_UTF8) && (!c->have_u8 || c->u8_gen != c->scan_gen || c->u8_nseg != nseg))
+    const uint32_t nseg = c->mg.nseg;
+    if ((classes & HVWS_C_TEXT_UTF8) && (!c->u8.have || c->u8.gen != c->scan_gen || c->u8.nseg != nseg))
         return set_err(HVWS_EINVAL, "hvws_check: HVWS_C_TEXT_UTF8 without an hvws_utf8 over the same scan");
     if (state_in)
         for (uint32_t s = 0; s < nseg; ++s)
             if (state_in[s] & ~(uint32_t)(HVWS_CK_OPEN | HVWS_CK_FAILED))
                 return set_err(HVWS_EINVAL, "hvws_check: state_in is no state hvws_get_check returns");
     // the record bound hvws_messages_rfc ran with, or the count read since
-    const uint64_t cap = std::min<uint64_t>(c->nfr, c->T().frame_cap);
-    const uint64_t pcap = c->mg_cap;
-    HIP_OR(c->ck_scan.ensure(check_scratch_bytes(cap)), HVWS_ENOMEM);
-    HIP_OR(c->ck_viol.ensure(cap + pcap + 16), HVWS_ENOMEM);
-    HIP_OR(c->ck_in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->ck_out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->ck_fail.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->ck_why.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(c->ck_code.ensure((uint64_t)nseg * 2 + 16), HVWS_ENOMEM);
-    c->have_chk = false;   // the tables are being rewritten
-    if (state_in && nseg) {
-        if (!c->ck_up_ev) HIP_OR(hipEventCreateWithFlags(&c->ck_up_ev, hipEventDisableTiming), HVWS_EHIP);
-        if (c->ck_up_pending) {   // the previous pass's copy out of the slot
-            HIP_OR(hipEventSynchronize(c->ck_up_ev), HVWS_EHIP);
-            c->ck_up_pending = false;
-        }
-        HIP_OR(c->h_ck_in.ensure((uint64_t)nseg * 4), HVWS_ENOMEM);
-        memcpy(c->h_ck_in.p, state_in, (uint64_t)nseg * 4);
-        HIP_OR(hipMemcpyAsync(c->ck_in.p, c->h_ck_in.p, (uint64_t)nseg * 4, hipMemcpyHostToDevice, c->stream),
-               HVWS_EHIP);
-        HIP_OR(hipEventRecord(c->ck_up_ev, c->stream), HVWS_EHIP);
-        c->ck_up_pending = true;
-    }
-    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    const uint64_t cap = record_bound(c);
+    const uint64_t pcap = c->mg.cap;
+    HIP_OR(c->ck.scan.ensure(check_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(c->ck.viol.ensure(cap + pcap + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck.in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck.out.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck.fail.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck.why.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(c->ck.code.ensure((uint64_t)nseg * 2 + 16), HVWS_ENOMEM);
+    c->ck.have = false;   // the tables are being rewritten
+    if ((rc = c->ck.up.send(c->ck.in.p, c->stream, state_in, (uint64_t)nseg * 4)) != HVWS_OK) return rc;
+    HIP_OR(timed_begin(c), HVWS_EHIP);
     HIP_OR(launch_check(c->T().f_info.as<uint32_t>(), c->T().f_length.as<uint64_t>(), c->T().total.as<uint64_t>(), cap,
-                        c->T().bases.as<uint64_t>(), nseg, c->mg_msgs.as<dmsg>(), c->mg_meta.as<uint64_t>(), pcap,
-                        c->mg_dout, c->mg_out_cap, c->u8_bad.as<uint64_t>(), classes, max_message,
-                        state_in ? c->ck_in.as<uint32_t>() : nullptr, c->ck_scan.p, c->ck_viol.as<uint8_t>(),
-                        c->ck_out.as<uint32_t>(), c->ck_fail.as<uint64_t>(), c->ck_why.as<uint32_t>(),
-                        c->ck_code.as<uint16_t>(), c->stream),
+                        c->T().bases.as<uint64_t>(), nseg, c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), pcap,
+                        c->mg.dout, c->mg.out_cap, c->u8.bad.as<uint64_t>(), classes, max_message,
+                        state_in ? c->ck.in.as<uint32_t>() : nullptr, c->ck.scan.p, c->ck.viol.as<uint8_t>(),
+                        c->ck.out.as<uint32_t>(), c->ck.fail.as<uint64_t>(), c->ck.why.as<uint32_t>(),
+                        c->ck.code.as<uint16_t>(), c->stream),
            HVWS_EHIP);
-    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-    c->ev_build = true;
-    // Pipelined steps: the scan two steps on writes this table set and must
-    // wait for this pass as it waits for the set's unmask.
-    if (c->piped) {
-        HIP_OR(hipEventRecord(c->T().free_ev, c->stream), HVWS_EHIP);
-        c->T().free_wait = c->T().free_ev;
-        c->T().free_pending = true;
-    }
-    c->have_chk = true;
-    c->ck_nseg = nseg;
-    c->ck_msg = c->msg_seq;
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    HIP_OR(hold_tables(c), HVWS_EHIP);
+    c->ck.have = true;
+    c->ck.nseg = nseg;
+    c->ck.msg = c->mg.seq;
     return HVWS_OK;
 }
 
 int hvws_get_check(hvws_ctx* c, uint32_t* state_out, uint64_t* fail_rec, uint32_t* why, uint16_t* code) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_chk) return set_err(HVWS_EINVAL, "no hvws_check call yet");
-    const uint64_t nseg = c->ck_nseg;
-    if (state_out && nseg)
-        HIP_OR(hipMemcpyAsync(state_out, c->ck_out.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (fail_rec && nseg)
-        HIP_OR(hipMemcpyAsync(fail_rec, c->ck_fail.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (why && nseg) HIP_OR(hipMemcpyAsync(why, c->ck_why.p, nseg * 4, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (code && nseg) HIP_OR(hipMemcpyAsync(code, c->ck_code.p, nseg * 2, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->ck.have) return set_err(HVWS_EINVAL, "no hvws_check call yet");
+    const uint64_t nseg = c->ck.nseg;
+    return read_rows(c, {{state_out, c->ck.out.p, nseg * 4},
+                         {fail_rec, c->ck.fail.p, nseg * 8},
+                         {why, c->ck.why.p, nseg * 4},
+                         {code, c->ck.code.p, nseg * 2}});
 }
 
 const uint64_t* hvws_check_device(hvws_ctx* c) {
-    if (!c || !c->have_chk) return nullptr;
-    return c->ck_fail.as<uint64_t>();
+    if (!c || !c->ck.have) return nullptr;
+    return c->ck.fail.as<uint64_t>();
 }
 
 const hvws_tx_msg* hvws_replies_device(hvws_ctx* c) {
-    if (!c || !c->have_rep) return nullptr;
-    return c->rp_msgs.as<hvws_tx_msg>();
+    if (!c || !c->rp.have) return nullptr;
+    return c->rp.msgs.as<hvws_tx_msg>();
 }
 
 const uint64_t* hvws_reply_count_device(hvws_ctx* c) {
-    if (!c || !c->have_rep) return nullptr;
-    return c->rp_scan.as<uint64_t>() + c->rp_cap;
+    if (!c || !c->rp.have) return nullptr;
+    return c->rp.scan.as<uint64_t>() + c->rp.cap;
 }
 
-uint64_t hvws_reply_capacity(hvws_ctx* c) { return c && c->have_rep ? c->rp_cap : 0; }
+uint64_t hvws_reply_capacity(hvws_ctx* c) { return c && c->rp.have ? c->rp.cap : 0; }
 
 int64_t hvws_reply_count(hvws_ctx* c) {
     if (check_ctx(c)) return -1;
-    if (!c->have_rep) {
+    if (!c->rp.have) {
         set_err(HVWS_EINVAL, "no hvws_replies call yet");
         return -1;
     }
-    uint64_t n = 0;
-    if (hipMemcpyAsync(&n, c->rp_scan.as<uint64_t>() + c->rp_cap, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_err(HVWS_EHIP, "hvws_reply_count: reading the count failed");
-        return -1;
-    }
-    return (int64_t)n;
+    return read_count(c, c->rp.scan.as<uint64_t>() + c->rp.cap, "hvws_reply_count");
 }
 
 int hvws_get_replies(hvws_ctx* c, hvws_tx_msg* out, uint64_t* piece, uint64_t first, uint64_t n) {
@@ -3759,35 +3768,21 @@ int hvws_get_replies(hvws_ctx* c, hvws_tx_msg* out, uint64_t* piece, uint64_t fi
     if (have < 0) return HVWS_EINVAL;
     if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "reply range out of bounds");
     if (n == 0) return HVWS_OK;
-    if (out)
-        HIP_OR(hipMemcpyAsync(out, c->rp_msgs.as<dtxmsg>() + first, n * sizeof(dtxmsg), hipMemcpyDeviceToHost, c->stream),
-               HVWS_EHIP);
-    if (piece)
-        HIP_OR(hipMemcpyAsync(piece, c->rp_piece.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost, c->stream),
-               HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    return read_rows(c, {{out, c->rp.msgs.as<dtxmsg>() + first, n * sizeof(dtxmsg)},
+                         {piece, c->rp.piece.as<uint64_t>() + first, n * 8}});
 }
 
 int hvws_get_segment_replies(hvws_ctx* c, uint64_t* first, uint64_t* count) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_rep) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
-    const uint64_t nseg = c->rp_nseg;
-    if (first && nseg) HIP_OR(hipMemcpyAsync(first, c->rp_first.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    if (count && nseg) HIP_OR(hipMemcpyAsync(count, c->rp_count.p, nseg * 8, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->rp.have) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
+    const uint64_t nseg = c->rp.nseg;
+    return read_rows(c, {{first, c->rp.first.p, nseg * 8}, {count, c->rp.count.p, nseg * 8}});
 }
 
 int hvws_get_reply_flags(hvws_ctx* c, uint8_t* out) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
-    if (!c->have_rep) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
-    const uint64_t nseg = c->rp_nseg;
-    if (out && nseg) HIP_OR(hipMemcpyAsync(out, c->rp_flags.p, nseg, hipMemcpyDeviceToHost, c->stream), HVWS_EHIP);
-    HIP_OR(hipStreamSynchronize(c->stream), HVWS_EHIP);
-    return HVWS_OK;
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->rp.have) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
+    return read_rows(c, {{out, c->rp.flags.p, c->rp.nseg}});
 }
 
 int hvws_encode_keys(hvws_ctx* c, const char* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
@@ -3797,11 +3792,10 @@ int hvws_encode_keys(hvws_ctx* c, const char* d_keys, const uint64_t* d_key_off,
     if (n == 0) return HVWS_OK;
     if (!d_keys || !d_key_off || !d_key_len || !d_accept) return set_err(HVWS_EINVAL, "encode_keys: null table");
     if (((uintptr_t)d_accept & 15u) != 0) return set_err(HVWS_EINVAL, "encode_keys: accept buffer must be 16-byte aligned");
-    HIP_OR(hipEventRecord(c->ev[4], c->stream), HVWS_EHIP);
+    HIP_OR(timed_begin(c), HVWS_EHIP);
     HIP_OR(launch_encode_keys((const uint8_t*)d_keys, d_key_off, d_key_len, n, (uint8_t*)d_accept, c->stream),
            HVWS_EHIP);
-    HIP_OR(hipEventRecord(c->ev[5], c->stream), HVWS_EHIP);
-    c->ev_build = true;
+    HIP_OR(timed_end(c), HVWS_EHIP);
     return HVWS_OK;
 }
 
@@ -3818,10 +3812,10 @@ const char* hvws_build_kernel_name(void) { return build_kernel_name(tx_variant(0
 
 const char* hvws_last_build_kernel(hvws_ctx* c) {
     if (!c) return "";
-    return build_kernel_name(c->tx_variant);
+    return build_kernel_name(c->tx.variant);
 }
 
-int hvws_last_build_uniform(hvws_ctx* c) { return c && c->tx_uniform ? 1 : 0; }
+int hvws_last_build_uniform(hvws_ctx* c) { return c && c->tx.uniform ? 1 : 0; }
 
 uint32_t hvws_set_validation(hvws_ctx* c, uint32_t classes) {
     if (!c) c = hvws::thread_ctx();
