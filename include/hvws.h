@@ -38,6 +38,9 @@
  *                PING, a CLOSE for the first CLOSE and nothing after it,
  *                optionally an echo of data messages -- as a message table
  *                hvws_send_messages sends without a host read in between.
+ *   hvws_fanout  TcpServerTmpl::broadcast / foreachChannel (evpp/TcpServer.h:
+ *                182-199) per topic: the reply table expanded through a
+ *                subscription table and ordered by destination connection.
  *   hvws_check   what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -921,6 +924,84 @@ int hvws_check(hvws_ctx* ctx, uint32_t classes, uint64_t max_message, const uint
 int hvws_get_check(hvws_ctx* ctx, uint32_t* state_out, uint64_t* fail_rec, uint32_t* why, uint16_t* code);
 const uint64_t* hvws_check_device(hvws_ctx* ctx);   /* fail_rec[] in device memory */
 int hvws_replies_checked(hvws_ctx* ctx, uint32_t policy, const uint8_t* closed_in);
+
+/* ---- fan-out to topic subscribers, device resident ------------------------ */
+/* hvws_replies answers the sender.  hvws_fanout delivers: it expands the reply
+ * table of the last hvws_replies / hvws_replies_checked through a subscription
+ * table and orders the result by destination connection, so that one
+ * hvws_send_messages builds the turn's whole output with every destination's
+ * bytes contiguous -- TcpServerTmpl::broadcast / foreachChannel
+ * (evpp/TcpServer.h) for a batch, without the host reading the reply table,
+ * walking the subscriptions and uploading a new table every turn.  What is
+ * selected is the reply call's business and is not restated here: deferred
+ * pieces, "close is final" and hvws_check's fail_rec apply as they do there
+ * (run the reply call with HVWS_R_ECHO: its TEXT / BINARY replies are the
+ * publications).
+ *
+ * Subscription table.  The caller's, in device memory, uploaded once
+ * (hvws_h2d) and kept across turns: topic t's subscribers are
+ * d_member[d_topic_first[t] .. d_topic_first[t + 1]), ntopics + 1 words and
+ * nmember ids.  A destination id is the caller's index of a connection in
+ * [0, ndest), ndest <= 2^31 - 1; it need not be a segment of this batch (a
+ * connection without a read still receives).  Removing a closed connection
+ * from the lists is the caller's job.  pub (host, nseg words, NULL = all
+ * HVWS_FAN_NONE): the topic segment s publishes to; dest_of (host, nseg
+ * words): segment s's own destination id.
+ *
+ * Edges.  R is the reply table, replies i = 0 .. nr - 1, op_i = flags & 0xF,
+ * s_i the segment of the piece reply i answers.
+ *   - op_i 1 or 2 is a publication.  With t = pub[s_i] not HVWS_FAN_NONE: one
+ *     edge (i, j) per listing j of topic t, to destination
+ *     d_member[d_topic_first[t] + j]; an edge to dest_of[s_i] is dropped unless
+ *     HVWS_FAN_SELF is set; a destination listed twice is delivered twice.
+ *     With t HVWS_FAN_NONE: no edges.
+ *   - any other opcode (PONG, CLOSE): exactly one edge (i, 0), to dest_of[s_i].
+ *
+ * Output.  A dense table, one hvws_tx_msg per delivery, holding R[i] unchanged
+ * (off / len still index the message call's d_out), sorted by the key
+ * (destination, op_i == 8, i, j) ascending: a destination's deliveries are in
+ * reply order -- sender order in the batch, then each sender's stream order --
+ * and that destination's own CLOSE reply is its last frame.  reply[k] is the i
+ * of delivery k; first[d] / count[d] destination d's range (a destination
+ * without deliveries: the next destination's first, count 0).  After
+ * hvws_send_messages(..., hvws_fanout_device, n, hvws_fanout_count_device, ...,
+ * masked = 0, d_msg_off, ...) with n = *out_deliveries, destination d's bytes
+ * are d_msg_off[first[d]] .. d_msg_off[first[d] + count[d]].
+ * hvws_get_reply_flags of the reply call stays valid; for an HVWS_RF_FAILED
+ * connection the host appends its 4-byte close behind dest_of[s]'s range.
+ *
+ * Waits once, as hvws_send_messages does: after the edge count the host reads
+ * the delivery total E and the bad count, and writes *out_deliveries = E
+ * (saturating).  HVWS_EINVAL, and the fanout getters then report none yet:
+ *   - no preceding reply call, or a message call or a scan on ctx since it;
+ *   - a flag bit other than HVWS_FAN_SELF; dest_of NULL or an entry >= ndest; a
+ *     pub entry >= ntopics that is not HVWS_FAN_NONE; ndest 0 or above 2^31 - 1;
+ *   - E > max_deliveries (*out_deliveries is still set), or more than 2^32 - 2
+ *     edges counted before self edges are dropped;
+ *   - a publication reaching a topic row with first[t] > first[t + 1] or
+ *     first[t + 1] > nmember, or a member id >= ndest.  A bad row or id that no
+ *     publication of the batch reaches is not looked at.
+ * No read leaves d_topic_first[0 .. ntopics] or d_member[0 .. nmember).
+ * Everything after the wait is asynchronous on the ctx stream;
+ * hvws_last_kernel_ms reports the device work after the wait (expansion, sort,
+ * finish) when this was the last call.  The tables are valid until the next
+ * hvws_fanout, hvws_replies* or hvws_messages* on ctx; the getters
+ * (hvws_fanout_device / hvws_fanout_count_device: d_msgs and d_n of
+ * hvws_send_messages, NULL = none; hvws_fanout_count; hvws_get_fanout:
+ * deliveries first .. first + n - 1 and the reply of each, either may be NULL;
+ * hvws_get_dest_fanout: ndest entries each, either may be NULL) report none
+ * after that, and the last two wait.  Results never depend on the kernels'
+ * geometry and are the same on every run.   */
+#define HVWS_FAN_NONE  UINT32_MAX
+#define HVWS_FAN_SELF  1u     /* a sender that subscribes to its own topic gets its message too */
+int hvws_fanout(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint32_t ntopics,
+                uint64_t nmember, uint32_t ndest, const uint32_t* pub, const uint32_t* dest_of, uint32_t flags,
+                uint64_t max_deliveries, uint64_t* out_deliveries);
+const hvws_tx_msg* hvws_fanout_device(hvws_ctx* ctx);
+const uint64_t* hvws_fanout_count_device(hvws_ctx* ctx);
+int64_t hvws_fanout_count(hvws_ctx* ctx);
+int hvws_get_fanout(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n);
+int hvws_get_dest_fanout(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -94,6 +94,8 @@ C_ALL = 63
 CK_OPEN, CK_FAILED = 1, 2
 CHECK_NONE = (1 << 64) - 1
 RF_FAILED = 4
+# HVWS_FAN_* (hvws_fanout)
+FAN_NONE, FAN_SELF = 0xFFFFFFFF, 1
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -223,6 +225,18 @@ _SIGS = {
     ),
     "hvws_check_device": (ctypes.c_void_p, [ctypes.c_void_p]),
     "hvws_replies_checked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "hvws_fanout": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "hvws_fanout_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_fanout_count_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_fanout_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_fanout": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
+    ),
+    "hvws_get_dest_fanout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -738,6 +752,49 @@ class Engine:
             ci = np.ascontiguousarray(closed_in, dtype=np.uint8)
         _check(lib().hvws_replies_checked(self.ctx, policy, ci.ctypes.data if ci is not None else None),
                "hvws_replies_checked")
+
+    def fanout(self, topic_first, member, ntopics: int, nmember: int, ndest: int, pub, dest_of, flags: int = 0,
+               max_deliveries: int = (1 << 64) - 1) -> int:
+        """hvws_fanout over the last replies() / replies_checked() call: its reply
+        table through the subscription table (topic_first, member: DeviceBuffers or
+        device addresses) into a delivery table ordered by destination.  pub: the
+        topic each segment publishes to (FAN_NONE: none; None = all none);
+        dest_of: each segment's own destination id.  Returns the deliveries;
+        last_deliveries holds them even when the call fails for max_deliveries."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        pb = np.ascontiguousarray(pub, dtype=np.uint32) if pub is not None else None
+        do = np.ascontiguousarray(dest_of, dtype=np.uint32) if dest_of is not None else None
+        n = ctypes.c_uint64(0)
+        rc = lib().hvws_fanout(self.ctx, dev(topic_first), dev(member), ntopics, nmember, ndest,
+                               pb.ctypes.data if pb is not None and pb.size else None,
+                               do.ctypes.data if do is not None else None, flags, max_deliveries, ctypes.byref(n))
+        self.last_deliveries = int(n.value)
+        _check(rc, "hvws_fanout")
+        return int(n.value)
+
+    def fanout_device(self) -> Tuple[int, int, int]:
+        """(table address, count word address, deliveries): msgs, d_n and n of
+        send_messages for the last fanout() call; (None, None, 0) when there is none."""
+        L = lib()
+        n = L.hvws_fanout_count(self.ctx)
+        return L.hvws_fanout_device(self.ctx), L.hvws_fanout_count_device(self.ctx), max(int(n), 0)
+
+    def fanout_table(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(deliveries [TX_MSG_DTYPE], the reply each carries) of the last fanout() call."""
+        n = lib().hvws_fanout_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_fanout_count")
+        out = np.zeros(n, dtype=TX_MSG_DTYPE)
+        reply = np.zeros(n, dtype=np.uint64)
+        _check(lib().hvws_get_fanout(self.ctx, out.ctypes.data, reply.ctypes.data, 0, n), "hvws_get_fanout")
+        return out, reply
+
+    def dest_fanout(self, ndest: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(first delivery, delivery count) per destination of the last fanout() call."""
+        first = np.zeros(max(ndest, 1), np.uint64)
+        cnt = np.zeros(max(ndest, 1), np.uint64)
+        _check(lib().hvws_get_dest_fanout(self.ctx, first.ctypes.data, cnt.ctypes.data), "hvws_get_dest_fanout")
+        return first[:ndest], cnt[:ndest]
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

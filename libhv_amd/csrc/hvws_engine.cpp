@@ -260,8 +260,29 @@ struct pass_replies {
     bool have = false;
     uint32_t nseg = 0;
     uint64_t cap = 0;
+    uint64_t gen = 0;   // the scans (scan_gen) before the last call
+    uint64_t seq = 0;   // reply calls so far
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&scan, &limit, &msgs, &piece, &first, &count, &flags, &closed});
+        up.release(ph);
+    }
+};
+
+// hvws_fanout: the edge scan's scratch, dest_of and pub per segment (they go up
+// through the slot in one copy), per segment {mark, self edges, bad}, {edges,
+// deliveries, bad, replies}, the sort's two pair arrays (keys, then values) and
+// its histograms, the delivery table and the reply of each delivery,
+// per-destination first / count.  rep / msg: the reply call (pass_replies::seq)
+// and the message call (pass_msg::seq) it expanded.
+struct pass_fan {
+    dbuf scan, in, seg, meta, ping, pong, hist, msgs, reply, first, count;
+    up_slot up;
+    bool have = false;
+    uint32_t ndest = 0;
+    uint64_t n = 0;   // deliveries
+    uint64_t rep = 0, msg = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &in, &seg, &meta, &ping, &pong, &hist, &msgs, &reply, &first, &count});
         up.release(ph);
     }
 };
@@ -389,6 +410,7 @@ struct hvws_ctx {
     pass_msg mg;
     pass_send sd;
     pass_replies rp;
+    pass_fan fan;
     pass_check ck;
     pass_tx tx;
     uint64_t scan_gen = 0;
@@ -2461,6 +2483,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->mg.release(ph);
         c->sd.release(ph);
         c->rp.release(ph);
+        c->fan.release(ph);
         c->ck.release(ph);
         c->tx.release(ph);
     };
@@ -3665,6 +3688,8 @@ int replies_pass(hvws_ctx* c, uint32_t policy, const uint8_t* closed_in, bool ch
     c->rp.have = true;
     c->rp.nseg = nseg;
     c->rp.cap = cap;
+    c->rp.gen = c->scan_gen;
+    ++c->rp.seq;
     return HVWS_OK;
 }
 }  // namespace
@@ -3783,6 +3808,129 @@ int hvws_get_reply_flags(hvws_ctx* c, uint8_t* out) {
     if (int rc = check_ctx(c)) return rc;
     if (!c->rp.have) return set_err(HVWS_EINVAL, "no hvws_replies call yet");
     return read_rows(c, {{out, c->rp.flags.p, c->rp.nseg}});
+}
+
+static_assert(HVWS_FAN_NONE == 0xFFFFFFFFu && HVWS_FAN_SELF == 1u, "fanout constants");
+
+// The last reply call's table through a subscription table, ordered by
+// destination (hvws_fan.hip): the edge count, one wait for {edges, deliveries,
+// bad}, then expansion, sort and finish.
+int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_member, uint32_t ntopics,
+                uint64_t nmember, uint32_t ndest, const uint32_t* pub, const uint32_t* dest_of, uint32_t flags,
+                uint64_t max_deliveries, uint64_t* out_deliveries) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_deliveries) *out_deliveries = 0;
+    c->fan.have = false;   // the tables are being rewritten
+    if (!c->rp.have || !c->mg.have) return set_err(HVWS_EINVAL, "hvws_fanout without a preceding hvws_replies");
+    if (c->rp.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_fanout: a scan has run since hvws_replies");
+    if (flags & ~(uint32_t)HVWS_FAN_SELF) return set_err(HVWS_EINVAL, "hvws_fanout: unknown flag bits");
+    if (!dest_of) return set_err(HVWS_EINVAL, "hvws_fanout: null dest_of");
+    if (ndest == 0 || ndest > 0x7FFFFFFFu)
+        return set_err(HVWS_EINVAL, "hvws_fanout: %u destinations (1 .. 2^31-1)", ndest);
+    const uint32_t nseg = c->rp.nseg;
+    bool publishes = false;
+    for (uint32_t s = 0; s < nseg; ++s) {
+        if (dest_of[s] >= ndest)
+            return set_err(HVWS_EINVAL, "hvws_fanout: dest_of[%u] = %u of %u destinations", s, dest_of[s], ndest);
+        if (pub && pub[s] != HVWS_FAN_NONE) {
+            if (pub[s] >= ntopics)
+                return set_err(HVWS_EINVAL, "hvws_fanout: pub[%u] = %u of %u topics", s, pub[s], ntopics);
+            publishes = true;
+        }
+    }
+    if (publishes && (!d_topic_first || (!d_member && nmember)))
+        return set_err(HVWS_EINVAL, "hvws_fanout: null subscription table");
+    const uint64_t cap = c->rp.cap;
+    // every reply and every edge has a 32-bit index
+    if (cap >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "hvws_fanout: %llu replies (max 2^32-2)", (unsigned long long)cap);
+    HIP_OR(c->fan.scan.ensure(fan_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(c->fan.in.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.seg.ensure((uint64_t)nseg * 16 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.meta.ensure(64), HVWS_ENOMEM);
+    // dest_of, then pub behind it
+    if ((rc = c->fan.up.send(c->fan.in.p, c->stream, dest_of, (uint64_t)nseg * 4, publishes ? pub : nullptr,
+                             publishes ? (uint64_t)nseg * 4 : 0)) != HVWS_OK)
+        return rc;
+    const fan_tables t{c->rp.msgs.as<dtxmsg>(), c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap,
+                       c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), c->mg.cap, nseg, c->fan.in.as<uint32_t>(),
+                       publishes ? c->fan.in.as<uint32_t>() + nseg : nullptr, d_topic_first, d_member, ntopics, nmember,
+                       ndest, (flags & HVWS_FAN_SELF) != 0};
+    uint64_t* selfc = c->fan.seg.as<uint64_t>();
+    uint32_t* mark = reinterpret_cast<uint32_t*>(selfc + nseg);
+    uint64_t* meta = c->fan.meta.as<uint64_t>();
+    HIP_OR(launch_fan_count(t, mark, selfc, mark + nseg, c->fan.scan.p, meta, c->stream), HVWS_EHIP);
+    // the one wait: [0] edges before the self drop, [1] deliveries, [2] bad replies, [3] replies
+    uint64_t h[4] = {0, 0, 0, 0};
+    if ((rc = read_rows(c, {{h, meta, sizeof h}})) != HVWS_OK) return rc;
+    const uint64_t nedges = h[0], ndel = h[1];
+    if (out_deliveries) *out_deliveries = ndel;
+    if (h[2])
+        return set_err(HVWS_EINVAL, "hvws_fanout: %llu publications reach a topic row outside the member table or a "
+                       "member id outside the destinations", (unsigned long long)h[2]);
+    if (ndel > max_deliveries)
+        return set_err(HVWS_EINVAL, "hvws_fanout: %llu deliveries, max_deliveries %llu", (unsigned long long)ndel,
+                       (unsigned long long)max_deliveries);
+    if (nedges > 0xFFFFFFFEull)
+        return set_err(HVWS_EINVAL, "hvws_fanout: %llu edges (max 2^32-2)", (unsigned long long)nedges);
+    HIP_OR(c->fan.ping.ensure(nedges * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.pong.ensure(nedges * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.hist.ensure(fan_hist_words(nedges) * 8), HVWS_ENOMEM);
+    HIP_OR(c->fan.msgs.ensure((ndel + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(c->fan.reply.ensure((ndel + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(c->fan.first.ensure((uint64_t)ndest * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.count.ensure((uint64_t)ndest * 8 + 16), HVWS_ENOMEM);
+    uint32_t* key[2] = {c->fan.ping.as<uint32_t>(), c->fan.pong.as<uint32_t>()};
+    uint32_t* val[2] = {key[0] + nedges, key[1] + nedges};
+    // the timed device work (hvws_last_kernel_ms): expansion, sort, finish
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_fan_deliver(t, c->fan.scan.p, nedges, ndel, key, val, c->fan.hist.as<uint64_t>(),
+                              c->fan.msgs.as<dtxmsg>(), c->fan.reply.as<uint64_t>(), c->fan.first.as<uint64_t>(),
+                              c->fan.count.as<uint64_t>(), c->stream),
+           HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    c->fan.have = true;
+    c->fan.ndest = ndest;
+    c->fan.n = ndel;
+    c->fan.rep = c->rp.seq;
+    c->fan.msg = c->mg.seq;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_fanout's tables stand: no reply or message call since.
+bool fan_valid(const hvws_ctx* c) {
+    return c && c->fan.have && c->rp.have && c->fan.rep == c->rp.seq && c->fan.msg == c->mg.seq;
+}
+}  // namespace
+
+const hvws_tx_msg* hvws_fanout_device(hvws_ctx* c) { return fan_valid(c) ? c->fan.msgs.as<hvws_tx_msg>() : nullptr; }
+
+const uint64_t* hvws_fanout_count_device(hvws_ctx* c) { return fan_valid(c) ? c->fan.meta.as<uint64_t>() + 1 : nullptr; }
+
+int64_t hvws_fanout_count(hvws_ctx* c) {
+    if (check_ctx(c)) return -1;
+    if (!fan_valid(c)) {
+        set_err(HVWS_EINVAL, "no hvws_fanout call yet");
+        return -1;
+    }
+    return (int64_t)c->fan.n;
+}
+
+int hvws_get_fanout(hvws_ctx* c, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n) {
+    const int64_t have = hvws_fanout_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "delivery range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{out, c->fan.msgs.as<dtxmsg>() + first, n * sizeof(dtxmsg)},
+                         {reply, c->fan.reply.as<uint64_t>() + first, n * 8}});
+}
+
+int hvws_get_dest_fanout(hvws_ctx* c, uint64_t* first, uint64_t* count) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!fan_valid(c)) return set_err(HVWS_EINVAL, "no hvws_fanout call yet");
+    const uint64_t nd = c->fan.ndest;
+    return read_rows(c, {{first, c->fan.first.p, nd * 8}, {count, c->fan.count.p, nd * 8}});
 }
 
 int hvws_encode_keys(hvws_ctx* c, const char* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,

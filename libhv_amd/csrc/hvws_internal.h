@@ -613,6 +613,48 @@ hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t ca
                           uint64_t* limit, uint64_t* scratch, dtxmsg* out, uint64_t* piece, uint64_t* rep_first,
                           uint64_t* rep_count, uint8_t* flags, bool by_rec, hipStream_t st,
                           const uint64_t* fail = nullptr);
+// hvws_fanout (hvws_fan.hip; include/hvws.h has the contract).  What its
+// kernels read: the reply table of launch_replies (rep, piece, the count word
+// clamped to rep_cap), the piece table it answers (pieces, mg_meta[2] clamped to
+// piece_cap), dest_of / pub per segment (device; pub may be null), and the
+// caller's subscription table.
+struct fan_tables {
+    const dtxmsg* rep;
+    const uint64_t* piece;
+    const uint64_t* nrep_dev;
+    uint64_t rep_cap;
+    const dmsg* pieces;
+    const uint64_t* mg_meta;
+    uint64_t piece_cap;
+    uint32_t nseg;
+    const uint32_t* dest_of;
+    const uint32_t* pub;
+    const uint64_t* topic_first;
+    const uint32_t* member;
+    uint32_t ntopics;
+    uint64_t nmember;
+    uint32_t ndest;
+    bool self;   // HVWS_FAN_SELF
+};
+uint64_t fan_scratch_bytes(uint64_t cap);      // the edge scan over cap replies
+uint32_t fan_sort_passes(uint32_t ndest);      // ceil(bits(2 ndest) / 8)
+uint64_t fan_sort_groups(uint64_t nedges);     // workgroups of a sort pass
+uint64_t fan_hist_words(uint64_t nedges);      // histogram, its scan and the scan's scratch
+// The edge count: mark (nseg words), selfc (nseg words of 8 bytes) and segbad
+// (nseg words) per segment, the scan in scratch (fan_scratch_bytes(rep_cap)),
+// then meta[0..3] = edges before the self drop, deliveries, bad replies (their
+// topic row leaves the member table, a member id is >= ndest, or their piece is
+// none of the batch), replies.  No read leaves topic_first[0 .. ntopics] or
+// member[0 .. nmember).
+hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* selfc, uint32_t* segbad, void* scratch,
+                            uint64_t* meta, hipStream_t st);
+// Expansion, sort and finish for nedges edges of which ndel are delivered (both
+// read by the host from meta, bad == 0): key / val are the ping-pong pair
+// arrays (nedges words each), hist fan_hist_words(nedges) words; out / reply:
+// ndel entries, first / count: ndest.
+hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_t nedges, uint64_t ndel, uint32_t* key[2],
+                              uint32_t* val[2], uint64_t* hist, dtxmsg* out, uint64_t* reply, uint64_t* first,
+                              uint64_t* count, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125
