@@ -353,7 +353,9 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
  * index and all three kernels), or of the last hvws_messages (table pass,
  * tile index and gather), or of the last hvws_send_messages' device work after
  * its wait (expansion, tile index, spans, k_build), or of the last hvws_check
- * (its scan and table kernels) -- whichever was called last; the default build
+ * (its scan and table kernels), or of the last hvws_fanout's device work after
+ * its wait (expansion, sort, finish), or of the last hvws_subs_update's after
+ * its wait (the placement) -- whichever was called last; the default build
  * geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
 const char* hvws_build_kernel_name(void);
@@ -939,12 +941,15 @@ int hvws_replies_checked(hvws_ctx* ctx, uint32_t policy, const uint8_t* closed_i
  * publications).
  *
  * Subscription table.  The caller's, in device memory, uploaded once
- * (hvws_h2d) and kept across turns: topic t's subscribers are
+ * (hvws_h2d), kept across turns and changed on the device by
+ * hvws_subs_update: topic t's subscribers are
  * d_member[d_topic_first[t] .. d_topic_first[t + 1]), ntopics + 1 words and
  * nmember ids.  A destination id is the caller's index of a connection in
  * [0, ndest), ndest <= 2^31 - 1; it need not be a segment of this batch (a
- * connection without a read still receives).  Removing a closed connection
- * from the lists is the caller's job.  pub (host, nseg words, NULL = all
+ * connection without a read still receives).  hvws_fanout itself never
+ * changes the lists: hvws_subs_update (below) removes the connections the
+ * reply call closed and applies the turn's joins and leaves, into the table
+ * the next turn's hvws_fanout reads.  pub (host, nseg words, NULL = all
  * HVWS_FAN_NONE): the topic segment s publishes to; dest_of (host, nseg
  * words): segment s's own destination id.
  *
@@ -1002,6 +1007,81 @@ const uint64_t* hvws_fanout_count_device(hvws_ctx* ctx);
 int64_t hvws_fanout_count(hvws_ctx* ctx);
 int hvws_get_fanout(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n);
 int hvws_get_dest_fanout(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+
+/* ---- the subscription table's upkeep, device resident ------------------------ */
+/* hvws_subs_update builds the next subscription table of hvws_fanout from the
+ * current one: the connections the last reply call closed are removed from
+ * every list, and a list of join / leave / drop events is applied -- what the
+ * reference's event loop does to its channel map (evpp/TcpServer.h) when a
+ * channel closes, for a whole turn, without the host reading the reply flags,
+ * rebuilding both arrays and uploading them.  The caller keeps two tables and
+ * alternates them, as the message calls alternate d_out: this call reads
+ * (d_topic_first, d_member) and writes (d_topic_first_out, d_member_out).
+ *
+ * The rule, stated sequentially.
+ *   1. Start from the rows L[t] = d_member[d_topic_first[t] .. d_topic_first[t + 1]).
+ *   2. dest_of (host, one word per segment of the last reply call, or NULL):
+ *      for every segment s whose reply flags hold HVWS_RF_CLOSED (an
+ *      HVWS_RF_FAILED connection carries it too), every listing of dest_of[s]
+ *      is removed from every row.  This happens before any event, so an event
+ *      that joins the same id again stands: the id may already belong to a new
+ *      connection.  NULL: no such drops, and no reply call is needed.
+ *   3. events (host, nev of them) in array order: HVWS_SUB_JOIN appends dest to
+ *      L[topic] -- under HVWS_SUBS_UNIQUE only if the row does not list dest at
+ *      that moment; HVWS_SUB_LEAVE removes every listing of dest from L[topic];
+ *      HVWS_SUB_DROP removes every listing of dest from every row (topic is
+ *      ignored).  HVWS_SUBS_UNIQUE does not remove duplicates the old table had.
+ *   4. Output: a dense table over the same ntopics, d_topic_first_out[0] = 0 and
+ *      d_topic_first_out[ntopics] = the new nmember.
+ *   5. Order within row t: the surviving listings of the old row in their old
+ *      order, then the surviving joined listings by destination id ascending,
+ *      then event order.  (hvws_fanout's result does not depend on the order
+ *      within a row; it is fixed so that the output is a function of the input.)
+ * In closed form, with stamp 0 for an old listing, 1 for the drops of step 2
+ * and e + 2 for event e: a listing survives iff no LEAVE of its (topic, dest)
+ * and no DROP of its dest has a stamp at or above its own.
+ *
+ * Waits once, as hvws_fanout does: after the counting kernels the host reads
+ * the new nmember, the counts and the bad flag, and writes *out_nmember.
+ * HVWS_EINVAL, with nothing written to either output array and
+ * hvws_subs_count then reporting none:
+ *   - an event op outside 1 .. 3, a JOIN / LEAVE topic >= ntopics, an event dest
+ *     >= ndest; a flag bit other than HVWS_SUBS_UNIQUE; ndest 0 or above
+ *     2^31 - 1; nmember or nev above 2^32 - 2;
+ *   - dest_of given without a preceding reply call, or with a scan on ctx since
+ *     it; a dest_of[s] >= ndest;
+ *   - an old table that is not dense -- d_topic_first[0] != 0, a decreasing pair,
+ *     d_topic_first[ntopics] != nmember -- or a member id >= ndest: this pass
+ *     reads the whole table, so every row counts (found on the device,
+ *     reported after the wait);
+ *   - a new nmember above member_cap (*out_nmember is still set);
+ *   - a NULL table where one is needed (d_member may be NULL only with nmember
+ *     0, d_member_out only with member_cap 0, events only with nev 0); an output
+ *     array overlapping an input array or the other output; an output array
+ *     that is not 16-byte aligned.
+ * nev == 0 with dest_of NULL is a valid compacting copy.  No read leaves
+ * d_topic_first[0 .. ntopics], d_member[0 .. nmember) or the reply call's
+ * flags; no write touches d_member_out at or beyond the new nmember or
+ * d_topic_first_out beyond ntopics + 1 words.  Everything after the wait is
+ * asynchronous on the ctx stream; hvws_last_kernel_ms reports it (the
+ * placement) when this was the last call.  The call neither reads nor
+ * invalidates the message, reply or fanout tables: after the reply call a turn
+ * may run hvws_fanout, hvws_send_messages and hvws_subs_update in any order.
+ * hvws_subs_count: the new nmember of the last call (-1: none);
+ * hvws_get_subs_counts: old listings kept, listings added, old listings
+ * removed, distinct destinations dropped under step 2.  Results never depend
+ * on the kernels' geometry and are the same on every run.   */
+#define HVWS_SUB_JOIN   1u   /* append dest to topic's row */
+#define HVWS_SUB_LEAVE  2u   /* remove every listing of dest from topic's row */
+#define HVWS_SUB_DROP   3u   /* remove every listing of dest from every row; topic is ignored */
+#define HVWS_SUBS_UNIQUE 1u  /* flags: a JOIN of a destination the row already lists adds nothing */
+typedef struct hvws_sub_event { uint32_t op, topic, dest; } hvws_sub_event;   /* 12 B */
+int hvws_subs_update(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint32_t ntopics,
+                     uint64_t nmember, uint32_t ndest, const hvws_sub_event* events, uint64_t nev,
+                     const uint32_t* dest_of, uint32_t flags, uint64_t* d_topic_first_out, uint32_t* d_member_out,
+                     uint64_t member_cap, uint64_t* out_nmember);
+int64_t hvws_subs_count(hvws_ctx* ctx);
+int hvws_get_subs_counts(hvws_ctx* ctx, uint64_t out[4]);
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -96,6 +96,11 @@ CHECK_NONE = (1 << 64) - 1
 RF_FAILED = 4
 # HVWS_FAN_* (hvws_fanout)
 FAN_NONE, FAN_SELF = 0xFFFFFFFF, 1
+# HVWS_SUB_*, HVWS_SUBS_UNIQUE and hvws_sub_event (hvws_subs_update)
+SUB_JOIN, SUB_LEAVE, SUB_DROP = 1, 2, 3
+SUBS_UNIQUE = 1
+SUB_EVENT_DTYPE = np.dtype([("op", "<u4"), ("topic", "<u4"), ("dest", "<u4")])
+assert SUB_EVENT_DTYPE.itemsize == 12
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -237,6 +242,14 @@ _SIGS = {
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     ),
     "hvws_get_dest_fanout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_subs_update": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "hvws_subs_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_subs_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -795,6 +808,37 @@ class Engine:
         cnt = np.zeros(max(ndest, 1), np.uint64)
         _check(lib().hvws_get_dest_fanout(self.ctx, first.ctypes.data, cnt.ctypes.data), "hvws_get_dest_fanout")
         return first[:ndest], cnt[:ndest]
+
+    def subs_update(self, topic_first, member, ntopics: int, nmember: int, ndest: int, events, dest_of,
+                    topic_first_out, member_out, member_cap: int, flags: int = 0) -> int:
+        """hvws_subs_update: the next subscription table (topic_first_out,
+        member_out: DeviceBuffers or device addresses, member_cap ids) from the
+        current one (topic_first, member), the events (SUB_EVENT_DTYPE, or
+        (op, topic, dest) triples) and, with dest_of (one id per segment of the
+        last reply call; None: no implicit drops), the connections that call
+        closed.  Returns the new nmember; last_subs_nmember holds it even when
+        the call fails for member_cap."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        if isinstance(events, np.ndarray) and events.dtype == SUB_EVENT_DTYPE:
+            ev = np.ascontiguousarray(events)
+        else:
+            ev = np.array([tuple(e) for e in events], dtype=SUB_EVENT_DTYPE)
+        do = np.ascontiguousarray(dest_of, dtype=np.uint32) if dest_of is not None else None
+        n = ctypes.c_uint64(0)
+        rc = lib().hvws_subs_update(self.ctx, dev(topic_first), dev(member), ntopics, nmember, ndest,
+                                    ev.ctypes.data if ev.size else None, ev.size,
+                                    do.ctypes.data if do is not None else None, flags, dev(topic_first_out),
+                                    dev(member_out), member_cap, ctypes.byref(n))
+        self.last_subs_nmember = int(n.value)
+        _check(rc, "hvws_subs_update")
+        return int(n.value)
+
+    def subs_counts(self) -> Tuple[int, int, int, int]:
+        """(old listings kept, listings added, old listings removed, destinations
+        dropped as closed) of the last subs_update() call."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hvws_get_subs_counts(self.ctx, out), "hvws_get_subs_counts")
+        return tuple(int(x) for x in out)
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

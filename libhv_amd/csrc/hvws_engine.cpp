@@ -287,6 +287,26 @@ struct pass_fan {
     }
 };
 
+// hvws_subs_update: the events with dest_of behind them (they go up through
+// the slot in one copy), the last drop stamp per destination, the sort's two
+// pair arrays (keys, then values) and its histograms, the sorted events as
+// (topic, destination) words, each topic's first of them, their ops / effective bits / "listed before"
+// marks (a byte each), the old listings' survive bits, the row of every 256th
+// listing, the ranks over the
+// events and over the listings, {new nmember, kept, added, removed, dropped,
+// bad} with the two counters behind them.  h: those counts on the host.
+struct pass_subs {
+    dbuf in, drop, ping, pong, hist, pk, evfirst, bits, surv, brow, erank, lrank, meta;
+    up_slot up;
+    bool have = false;
+    uint64_t h[6] = {0, 0, 0, 0, 0, 0};
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&in, &drop, &ping, &pong, &hist, &pk, &evfirst, &bits, &surv, &brow, &erank, &lrank,
+                                        &meta});
+        up.release(ph);
+    }
+};
+
 // hvws_check: the sequence scan's scratch, one byte of violation classes per
 // record and piece, per-connection state in / out, fail_rec, why and code;
 // state_in goes up through the slot.  msg: the message call (pass_msg::seq)
@@ -411,6 +431,7 @@ struct hvws_ctx {
     pass_send sd;
     pass_replies rp;
     pass_fan fan;
+    pass_subs subs;
     pass_check ck;
     pass_tx tx;
     uint64_t scan_gen = 0;
@@ -2484,6 +2505,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->sd.release(ph);
         c->rp.release(ph);
         c->fan.release(ph);
+        c->subs.release(ph);
         c->ck.release(ph);
         c->tx.release(ph);
     };
@@ -3931,6 +3953,134 @@ int hvws_get_dest_fanout(hvws_ctx* c, uint64_t* first, uint64_t* count) {
     if (!fan_valid(c)) return set_err(HVWS_EINVAL, "no hvws_fanout call yet");
     const uint64_t nd = c->fan.ndest;
     return read_rows(c, {{first, c->fan.first.p, nd * 8}, {count, c->fan.count.p, nd * 8}});
+}
+
+static_assert(HVWS_SUB_JOIN == 1u && HVWS_SUB_LEAVE == 2u && HVWS_SUB_DROP == 3u && HVWS_SUBS_UNIQUE == 1u &&
+                  sizeof(hvws_sub_event) == 12 && sizeof(dsubev) == sizeof(hvws_sub_event) &&
+                  RF_CLOSED == HVWS_RF_CLOSED,
+              "subscription update constants");
+
+namespace {
+bool ranges_meet(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+}  // namespace
+
+// The next subscription table from the current one (hvws_subs.hip): drops,
+// the pair sort, survive and effective bits and their scans, one wait for the
+// counts, then the placement.
+int hvws_subs_update(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_member, uint32_t ntopics,
+                     uint64_t nmember, uint32_t ndest, const hvws_sub_event* events, uint64_t nev,
+                     const uint32_t* dest_of, uint32_t flags, uint64_t* d_topic_first_out, uint32_t* d_member_out,
+                     uint64_t member_cap, uint64_t* out_nmember) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_nmember) *out_nmember = 0;
+    c->subs.have = false;
+    if (flags & ~(uint32_t)HVWS_SUBS_UNIQUE) return set_err(HVWS_EINVAL, "hvws_subs_update: unknown flag bits");
+    if (ndest == 0 || ndest > 0x7FFFFFFFu)
+        return set_err(HVWS_EINVAL, "hvws_subs_update: %u destinations (1 .. 2^31-1)", ndest);
+    if (nmember > 0xFFFFFFFEull || nev > 0xFFFFFFFEull)
+        return set_err(HVWS_EINVAL, "hvws_subs_update: %llu listings, %llu events (max 2^32-2 each)",
+                       (unsigned long long)nmember, (unsigned long long)nev);
+    if (!d_topic_first || !d_topic_first_out || (!d_member && nmember) || (!d_member_out && member_cap) ||
+        (!events && nev))
+        return set_err(HVWS_EINVAL, "hvws_subs_update: null table");
+    if (((uintptr_t)d_topic_first_out & 15u) || ((uintptr_t)d_member_out & 15u))
+        return set_err(HVWS_EINVAL, "hvws_subs_update: the output arrays must be 16-byte aligned");
+    const uint64_t fb = ((uint64_t)ntopics + 1) * 8, mb = std::min<uint64_t>(member_cap, 1ull << 32) * 4;
+    if (ranges_meet(d_topic_first_out, fb, d_topic_first, fb) || ranges_meet(d_topic_first_out, fb, d_member, nmember * 4) ||
+        ranges_meet(d_member_out, mb, d_topic_first, fb) || ranges_meet(d_member_out, mb, d_member, nmember * 4) ||
+        ranges_meet(d_member_out, mb, d_topic_first_out, fb))
+        return set_err(HVWS_EINVAL, "hvws_subs_update: an output array overlaps another array of the call");
+    for (uint64_t e = 0; e < nev; ++e) {
+        const hvws_sub_event& v = events[e];
+        if (v.op < HVWS_SUB_JOIN || v.op > HVWS_SUB_DROP)
+            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].op = %u", (unsigned long long)e, v.op);
+        if (v.op != HVWS_SUB_DROP && v.topic >= ntopics)
+            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].topic = %u of %u topics", (unsigned long long)e,
+                           v.topic, ntopics);
+        if (v.dest >= ndest)
+            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].dest = %u of %u destinations",
+                           (unsigned long long)e, v.dest, ndest);
+    }
+    uint32_t nseg = 0;
+    if (dest_of) {
+        if (!c->rp.have) return set_err(HVWS_EINVAL, "hvws_subs_update: dest_of without a preceding hvws_replies");
+        if (c->rp.gen != c->scan_gen)
+            return set_err(HVWS_EINVAL, "hvws_subs_update: a scan has run since hvws_replies");
+        nseg = c->rp.nseg;
+        for (uint32_t s = 0; s < nseg; ++s)
+            if (dest_of[s] >= ndest)
+                return set_err(HVWS_EINVAL, "hvws_subs_update: dest_of[%u] = %u of %u destinations", s, dest_of[s], ndest);
+    }
+    pass_subs& p = c->subs;
+    HIP_OR(p.in.ensure(nev * 12 + (uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.drop.ensure((uint64_t)ndest * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.ping.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.pong.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.hist.ensure(fan_hist_words(nev) * 8), HVWS_ENOMEM);
+    HIP_OR(p.pk.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.evfirst.ensure(((uint64_t)ntopics + 1) * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.bits.ensure(nev * 3 + 16), HVWS_ENOMEM);
+    HIP_OR(p.surv.ensure(nmember + 16), HVWS_ENOMEM);
+    HIP_OR(p.brow.ensure((nmember / 256 + 2) * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.erank.ensure(subs_event_rank_words(nev) * 8), HVWS_ENOMEM);
+    HIP_OR(p.lrank.ensure(subs_rank_words(nmember) * 8), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(128), HVWS_ENOMEM);
+    // the events, then dest_of behind them
+    const bool drops = dest_of && nseg;
+    if (nev)
+        rc = p.up.send(p.in.p, c->stream, events, nev * 12, drops ? dest_of : nullptr, drops ? (uint64_t)nseg * 4 : 0);
+    else
+        rc = p.up.send(p.in.p, c->stream, drops ? dest_of : nullptr, (uint64_t)nseg * 4);
+    if (rc != HVWS_OK) return rc;
+    const subs_tables t{d_topic_first, d_member, ntopics, nmember, ndest, p.in.as<dsubev>(), nev,
+                        drops ? reinterpret_cast<const uint32_t*>(p.in.as<uint8_t>() + nev * 12) : nullptr,
+                        drops ? c->rp.flags.as<uint8_t>() : nullptr, drops ? nseg : 0u,
+                        (flags & HVWS_SUBS_UNIQUE) != 0};
+    uint32_t* key0 = p.ping.as<uint32_t>();
+    uint32_t* key1 = p.pong.as<uint32_t>();
+    uint8_t* bits = p.bits.as<uint8_t>();
+    const subs_work w{p.drop.as<uint32_t>(), {key0, key1}, {key0 + nev, key1 + nev}, p.hist.as<uint64_t>(),
+                      p.pk.as<uint64_t>(), p.evfirst.as<uint64_t>(), bits, bits + nev, bits + 2 * nev, p.surv.as<uint8_t>(), p.brow.as<uint32_t>(),
+                      p.erank.as<uint64_t>(), p.lrank.as<uint64_t>(), p.meta.as<uint64_t>()};
+    HIP_OR(launch_subs_count(t, w, c->stream), HVWS_EHIP);
+    // the one wait: new nmember, kept, added, removed, destinations dropped as closed, bad
+    uint64_t h[6] = {0, 0, 0, 0, 0, 0};
+    if ((rc = read_rows(c, {{h, w.meta, sizeof h}})) != HVWS_OK) return rc;
+    if (h[5])
+        return set_err(HVWS_EINVAL, "hvws_subs_update: the table is not dense (topic_first[0] != 0, a decreasing pair, "
+                       "topic_first[ntopics] != nmember) or holds a member id outside the destinations");
+    if (out_nmember) *out_nmember = h[0];
+    if (h[0] > member_cap)
+        return set_err(HVWS_EINVAL, "hvws_subs_update: %llu listings, member_cap %llu", (unsigned long long)h[0],
+                       (unsigned long long)member_cap);
+    // the timed device work (hvws_last_kernel_ms): the placement
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_subs_place(t, w, h[0], d_topic_first_out, d_member_out, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    memcpy(p.h, h, sizeof h);
+    return HVWS_OK;
+}
+
+int64_t hvws_subs_count(hvws_ctx* c) {
+    if (check_ctx(c)) return -1;
+    if (!c->subs.have) {
+        set_err(HVWS_EINVAL, "no hvws_subs_update call yet");
+        return -1;
+    }
+    return (int64_t)c->subs.h[0];
+}
+
+int hvws_get_subs_counts(hvws_ctx* c, uint64_t out[4]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->subs.have) return set_err(HVWS_EINVAL, "no hvws_subs_update call yet");
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_subs_counts: null out");
+    for (int k = 0; k < 4; ++k) out[k] = c->subs.h[1 + k];
+    return HVWS_OK;
 }
 
 int hvws_encode_keys(hvws_ctx* c, const char* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,

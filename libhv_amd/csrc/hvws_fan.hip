@@ -300,11 +300,12 @@ __global__ __launch_bounds__(256) void k_fan_dests(const uint32_t* __restrict__ 
 }  // namespace
 
 uint64_t fan_scratch_bytes(uint64_t cap) { return (cap + 16 + scan_tmp_words(cap)) * sizeof(fan3); }
-uint32_t fan_sort_passes(uint32_t ndest) {
+uint32_t fan_key_passes(uint64_t max_key) {
     uint32_t bits = 0;
-    for (uint64_t v = 2ull * ndest; v; v >>= 1) ++bits;
+    for (uint64_t v = max_key; v; v >>= 1) ++bits;
     return (bits + 7) / 8;
 }
+uint32_t fan_sort_passes(uint32_t ndest) { return fan_key_passes(2ull * ndest); }
 uint64_t fan_sort_groups(uint64_t nedges) { return (nedges + FAN_TILE - 1) / FAN_TILE; }
 uint64_t fan_hist_words(uint64_t nedges) {
     const uint64_t h = 256 * fan_sort_groups(nedges);
@@ -332,6 +333,25 @@ hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* self
     return hipGetLastError();
 }
 
+hipError_t launch_fan_sort(uint32_t* const key[2], uint32_t* const val[2], uint64_t n, uint32_t passes, uint64_t* hist,
+                           int* cur, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const uint64_t nwg = fan_sort_groups(n), h = 256 * nwg;
+    uint64_t* base = hist + h;
+    uint64_t* total = base + h;   // one value; 16 are set aside
+    uint64_t* tmp = total + 16;
+    int c = *cur;
+    for (uint32_t p = 0; p < passes; ++p, c ^= 1) {
+        hipLaunchKernelGGL(k_fan_hist, dim3((uint32_t)nwg), dim3(FAN_T), 0, st, key[c], n, 8 * p, hist);
+        const hipError_t e = launch_scan_of(scan_from_array<uint64_t>{hist}, base, h, tmp, total, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_fan_scatter, dim3((uint32_t)nwg), dim3(FAN_T), 0, st, key[c], val[c], n, 8 * p, base,
+                           key[c ^ 1], val[c ^ 1]);
+    }
+    *cur = c;
+    return hipGetLastError();
+}
+
 hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_t nedges, uint64_t ndel, uint32_t* key[2],
                               uint32_t* val[2], uint64_t* hist, dtxmsg* out, uint64_t* reply, uint64_t* first,
                               uint64_t* count, hipStream_t st) {
@@ -341,18 +361,8 @@ hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_
                            reinterpret_cast<const fan3*>(scratch), nedges, key[0], val[0]);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        const uint64_t nwg = fan_sort_groups(nedges), h = 256 * nwg;
-        uint64_t* base = hist + h;
-        uint64_t* total = base + h;   // one value; 16 are set aside
-        uint64_t* tmp = total + 16;
-        const uint32_t passes = fan_sort_passes(in.ndest);
-        for (uint32_t p = 0; p < passes; ++p, cur ^= 1) {
-            hipLaunchKernelGGL(k_fan_hist, dim3((uint32_t)nwg), dim3(FAN_T), 0, st, key[cur], nedges, 8 * p, hist);
-            e = launch_scan_of(scan_from_array<uint64_t>{hist}, base, h, tmp, total, st);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_fan_scatter, dim3((uint32_t)nwg), dim3(FAN_T), 0, st, key[cur], val[cur], nedges,
-                               8 * p, base, key[cur ^ 1], val[cur ^ 1]);
-        }
+        e = launch_fan_sort(key, val, nedges, fan_sort_passes(in.ndest), hist, &cur, st);
+        if (e != hipSuccess) return e;
         if (ndel)
             hipLaunchKernelGGL(k_fan_rows, dim3((uint32_t)((ndel + 255) / 256)), dim3(256), 0, st, val[cur], ndel, in.rep,
                                out, reply);

@@ -655,6 +655,65 @@ hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* self
 hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_t nedges, uint64_t ndel, uint32_t* key[2],
                               uint32_t* val[2], uint64_t* hist, dtxmsg* out, uint64_t* reply, uint64_t* first,
                               uint64_t* count, hipStream_t st);
+// The sort of launch_fan_deliver on its own: n pairs by the low 8 * passes bits
+// of their keys, stable, between the ping-pong arrays; *cur says which of the
+// two holds the pairs, before and after.  hist: fan_hist_words(n) words.
+uint32_t fan_key_passes(uint64_t max_key);     // ceil(bits(max_key) / 8)
+hipError_t launch_fan_sort(uint32_t* const key[2], uint32_t* const val[2], uint64_t n, uint32_t passes, uint64_t* hist,
+                           int* cur, hipStream_t st);
+// hvws_subs_update (hvws_subs.hip; include/hvws.h has the contract).  dsubev
+// mirrors hvws_sub_event.  What its kernels read: the caller's table, the
+// events and dest_of (device copies; dest_of null: no implicit drops) and the
+// reply call's per-segment flags.
+struct dsubev {
+    uint32_t op, topic, dest;
+};
+struct subs_tables {
+    const uint64_t* topic_first;
+    const uint32_t* member;
+    uint32_t ntopics;
+    uint64_t nmember;
+    uint32_t ndest;
+    const dsubev* ev;
+    uint64_t nev;
+    const uint32_t* dest_of;
+    const uint8_t* rflags;
+    uint32_t nseg;
+    bool unique;   // HVWS_SUBS_UNIQUE
+};
+// Its work areas: drop (ndest words), the sort's pair arrays (nev words each)
+// and hist (fan_hist_words(nev)), pk (nev words of 8 bytes), evfirst
+// (ntopics + 1 words of 8 bytes: each topic's first sorted event), kind / eff / listed
+// (nev bytes each), surv (nmember bytes), brow (nmember / 256 + 2 words: the
+// row of every 256th listing), erank (subs_event_rank_words(nev)),
+// lrank (subs_rank_words(nmember)), meta (10 words of 8 bytes).
+struct subs_work {
+    uint32_t* drop;
+    uint32_t* key[2];
+    uint32_t* val[2];
+    uint64_t* hist;
+    uint64_t* pk;
+    uint64_t* evfirst;
+    uint8_t* kind;
+    uint8_t* eff;
+    uint8_t* listed;
+    uint8_t* surv;
+    uint32_t* brow;
+    uint64_t* erank;
+    uint64_t* lrank;
+    uint64_t* meta;
+};
+uint64_t subs_rank_words(uint64_t n);
+uint64_t subs_event_rank_words(uint64_t nev);
+// Everything up to the counts: meta[0..5] = new nmember, listings kept, added,
+// removed, destinations dropped as closed, bad (the table is not dense or holds
+// a member id >= ndest).  No read leaves topic_first[0 .. ntopics],
+// member[0 .. nmember) or rflags[0 .. nseg); neither output is touched.
+hipError_t launch_subs_count(const subs_tables& t, const subs_work& w, hipStream_t st);
+// The placement, for a table launch_subs_count found good: first_out
+// (ntopics + 1 words) and member_out[0 .. newn).
+hipError_t launch_subs_place(const subs_tables& t, const subs_work& w, uint64_t newn, uint64_t* first_out,
+                             uint32_t* member_out, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125
