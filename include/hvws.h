@@ -41,7 +41,10 @@
  *   hvws_fanout  TcpServerTmpl::broadcast / foreachChannel (evpp/TcpServer.h:
  *                182-199) per topic: the reply table expanded through a
  *                subscription table and ordered by destination connection.
- *   hvws_check   what the reference leaves out altogether: failing a connection
+ *   hvws_budget  hio_write's over-limit rule (event/nio.c:554-560) for that
+ *                table: every destination's deliveries cut at its byte budget,
+ *                the destinations that went over, each one's byte range.
+ *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
  *   hvws_wsp_*   C handle over the WebSocketParser class
@@ -354,7 +357,8 @@ int hvws_build_frames(hvws_ctx* ctx, uint8_t* d_out, uint64_t out_cap, const uin
  * tile index and gather), or of the last hvws_send_messages' device work after
  * its wait (expansion, tile index, spans, k_build), or of the last hvws_check
  * (its scan and table kernels), or of the last hvws_fanout's device work after
- * its wait (expansion, sort, finish), or of the last hvws_subs_update's after
+ * its wait (expansion, sort, finish), or of the last hvws_budget (all of it),
+ * or of the last hvws_subs_update's after
  * its wait (the placement) -- whichever was called last; the default build
  * geometry's name. */
 int hvws_last_kernel_ms(hvws_ctx* ctx, float* ms);
@@ -1007,6 +1011,82 @@ const uint64_t* hvws_fanout_count_device(hvws_ctx* ctx);
 int64_t hvws_fanout_count(hvws_ctx* ctx);
 int hvws_get_fanout(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n);
 int hvws_get_dest_fanout(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+
+/* ---- per-destination write limits for the fan-out, device resident ---------- */
+/* hvws_budget cuts every destination's deliveries of the last hvws_fanout at
+ * the number of bytes that destination may still be sent, before a byte is
+ * built: hio_write's rule (event/nio.c:554-560) -- a write whose unwritten bytes
+ * would take the channel's write_bufsize above max_write_bufsize
+ * (MAX_WRITE_BUFSIZE, 16 MiB, event/hevent.h:20; Channel::setMaxWriteBufsize,
+ * evpp/Channel.h:178) fails with ERR_OVER_LIMIT and the channel is closed --
+ * for the whole delivery table, without the host reading the table, sizing
+ * every delivery, walking every range and uploading a filtered table.  It
+ * runs between hvws_fanout and hvws_send_messages and does not wait.
+ *
+ * Input.  The last valid hvws_fanout on ctx (no reply or message call since,
+ * and no scan since its reply call): its delivery table T[0 .. n), reply[] and
+ * first[d] / count[d], ndest that call's.  d_budget: the caller's array in
+ * device memory, ndest words, uploaded with hvws_h2d and kept across turns like
+ * the subscription table; NULL: every destination's budget is budget_all
+ * (ignored otherwise).  A budget is the bytes the destination may still be
+ * sent -- its max_write_bufsize minus what its socket has queued; UINT64_MAX:
+ * unlimited; every value is valid.  fragment and masked are those the
+ * following hvws_send_messages will be given.
+ *
+ * Wire size.  w_k: the bytes hvws_send_messages emits for delivery k under that
+ * fragment and masked -- websocket_calc_frame_size summed over the frames of
+ * WebSocketChannel::send's fragmentation.
+ *
+ * Rule.  For destination d, over k = first[d] .. first[d] + count[d] - 1 in
+ * table order, c_k = the sum of w_q over first[d] <= q <= k; delivery k is kept
+ * iff c_k <= budget[d] (equality keeps it, as nio.c:556 does).  Sizes are
+ * positive, so the kept deliveries are a prefix of the range: a destination
+ * with a dropped delivery gets HVWS_BF_OVER, and nothing at or behind its first
+ * dropped delivery goes out -- not a smaller delivery either, nor its own CLOSE
+ * reply: the channel is closed.  A destination without deliveries is never
+ * OVER; a budget of 0 drops everything.  One deviation: the reference applies
+ * the check per write, that is per frame, so a fragmented message can be cut
+ * between two fragments; this pass cuts at message boundaries -- a message
+ * whose frames do not all fit is not started.  
+ *
+ * Output.  A dense table of the kept deliveries in the old order, hvws_tx_msg
+ * rows unchanged; reply[k], the reply index of kept delivery k; the kept count
+ * as a device word; per destination first[d] / count[d] in the new table
+ * (hvws_get_dest_fanout's convention for a destination without deliveries),
+ * flags[d], and byte_off, ndest + 1 words: the exclusive sum of the
+ * destinations' kept wire bytes, its last word the total.  So after
+ * hvws_send_messages(..., hvws_budget_device, n = hvws_fanout_count,
+ * hvws_budget_count_device, fragment, masked, d_msg_off, ...) destination d's
+ * bytes are byte_off[d] .. byte_off[d + 1], equal to d_msg_off[first[d]] ..
+ * d_msg_off[first[d] + count[d]], and out[1] of the totals is that call's
+ * exact *out_len: the out_cap to allocate.  The host closes the OVER
+ * destinations and passes them to hvws_subs_update as HVWS_SUB_DROP events.
+ *
+ * Asynchronous on the ctx stream, no wait; hvws_last_kernel_ms reports it when
+ * it was the last call.  It writes nothing the fan-out's getters, the reply
+ * call or the message call read: hvws_fanout_device stays valid beside it.
+ * HVWS_EINVAL with nothing launched: no valid hvws_fanout; masked not 0 or 1;
+ * (fan-out count) x (wire size of one message of the message call's out_cap
+ * bytes under fragment / masked) does not fit 64 bits -- checked on the host,
+ * so no device sum can wrap.  No read leaves d_budget[0 .. ndest).  The
+ * results are valid until the next hvws_budget, hvws_fanout, hvws_replies*,
+ * hvws_messages* or scan on ctx; the getters (hvws_budget_device /
+ * hvws_budget_count_device: d_msgs and d_n of hvws_send_messages, NULL = none;
+ * hvws_budget_count: the kept deliveries, -1 = none; hvws_get_budget: kept
+ * deliveries first .. first + n - 1 and the reply of each, either may be NULL;
+ * hvws_get_dest_budget: ndest entries each, ndest + 1 for byte_off, any may be
+ * NULL; hvws_get_budget_totals: kept deliveries, kept bytes, dropped
+ * deliveries, destinations over) report none after that, and all but the first
+ * two wait.  Results never depend on the kernels' geometry and are the same on
+ * every run.   */
+#define HVWS_BF_OVER 1u   /* the destination's deliveries were cut: the host closes it (ERR_OVER_LIMIT) */
+int hvws_budget(hvws_ctx* ctx, const uint64_t* d_budget, uint64_t budget_all, uint64_t fragment, int masked);
+const hvws_tx_msg* hvws_budget_device(hvws_ctx* ctx);        /* d_msgs of hvws_send_messages */
+const uint64_t*    hvws_budget_count_device(hvws_ctx* ctx);  /* its d_n; its n is hvws_fanout_count */
+int64_t hvws_budget_count(hvws_ctx* ctx);                    /* kept deliveries; waits; -1: none */
+int hvws_get_budget(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n);
+int hvws_get_dest_budget(hvws_ctx* ctx, uint64_t* first, uint64_t* count, uint64_t* byte_off, uint8_t* flags);
+int hvws_get_budget_totals(hvws_ctx* ctx, uint64_t out[4]);  /* kept deliveries, kept bytes, dropped deliveries, destinations over */
 
 /* ---- the subscription table's upkeep, device resident ------------------------ */
 /* hvws_subs_update builds the next subscription table of hvws_fanout from the

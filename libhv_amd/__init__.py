@@ -96,6 +96,8 @@ CHECK_NONE = (1 << 64) - 1
 RF_FAILED = 4
 # HVWS_FAN_* (hvws_fanout)
 FAN_NONE, FAN_SELF = 0xFFFFFFFF, 1
+# HVWS_BF_* (hvws_budget)
+BF_OVER = 1
 # HVWS_SUB_*, HVWS_SUBS_UNIQUE and hvws_sub_event (hvws_subs_update)
 SUB_JOIN, SUB_LEAVE, SUB_DROP = 1, 2, 3
 SUBS_UNIQUE = 1
@@ -242,6 +244,19 @@ _SIGS = {
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     ),
     "hvws_get_dest_fanout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_budget": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    ),
+    "hvws_budget_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_budget_count_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_budget_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_budget": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
+    ),
+    "hvws_get_dest_budget": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    ),
+    "hvws_get_budget_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "hvws_subs_update": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
@@ -808,6 +823,51 @@ class Engine:
         cnt = np.zeros(max(ndest, 1), np.uint64)
         _check(lib().hvws_get_dest_fanout(self.ctx, first.ctypes.data, cnt.ctypes.data), "hvws_get_dest_fanout")
         return first[:ndest], cnt[:ndest]
+
+    def budget(self, budget, budget_all: int = (1 << 64) - 1, fragment: int = 0, masked: bool = False) -> None:
+        """hvws_budget over the last fanout() call: every destination's deliveries
+        cut at its byte budget.  budget: ndest words of 8 bytes in device memory (a
+        DeviceBuffer or a device address), or None: budget_all for every
+        destination.  fragment / masked: those of the send_messages() that
+        follows.  No wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_budget(self.ctx, dev(budget), budget_all, fragment, int(masked)), "hvws_budget")
+
+    def budget_device(self) -> Tuple[int, int, int]:
+        """(table address, count word address, the fan-out's deliveries): msgs, d_n
+        and n of send_messages for the last budget() call; (None, None, 0) when
+        there is none.  No wait."""
+        L = lib()
+        table, d_n = L.hvws_budget_device(self.ctx), L.hvws_budget_count_device(self.ctx)
+        return table, d_n, max(int(L.hvws_fanout_count(self.ctx)), 0) if table else 0
+
+    def budget_table(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(kept deliveries [TX_MSG_DTYPE], the reply each carries) of the last budget() call."""
+        n = lib().hvws_budget_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_budget_count")
+        out = np.zeros(n, dtype=TX_MSG_DTYPE)
+        reply = np.zeros(n, dtype=np.uint64)
+        _check(lib().hvws_get_budget(self.ctx, out.ctypes.data, reply.ctypes.data, 0, n), "hvws_get_budget")
+        return out, reply
+
+    def dest_budget(self, ndest: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(first kept delivery, kept count, byte_off [ndest + 1], BF_* flags) per
+        destination of the last budget() call."""
+        first = np.zeros(max(ndest, 1), np.uint64)
+        cnt = np.zeros(max(ndest, 1), np.uint64)
+        off = np.zeros(ndest + 1, np.uint64)
+        flags = np.zeros(max(ndest, 1), np.uint8)
+        _check(lib().hvws_get_dest_budget(self.ctx, first.ctypes.data, cnt.ctypes.data, off.ctypes.data,
+                                          flags.ctypes.data), "hvws_get_dest_budget")
+        return first[:ndest], cnt[:ndest], off, flags[:ndest]
+
+    def budget_totals(self) -> Tuple[int, int, int, int]:
+        """(kept deliveries, kept bytes, dropped deliveries, destinations over) of
+        the last budget() call; the kept bytes are the exact length of the send."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hvws_get_budget_totals(self.ctx, out), "hvws_get_budget_totals")
+        return tuple(int(x) for x in out)
 
     def subs_update(self, topic_first, member, ntopics: int, nmember: int, ndest: int, events, dest_of,
                     topic_first_out, member_out, member_cap: int, flags: int = 0) -> int:

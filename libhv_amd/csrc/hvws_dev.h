@@ -200,6 +200,26 @@ hipError_t launch_scan_of(LOAD load, V* out, uint64_t n, V* tmp, V* total, hipSt
     return hipGetLastError();
 }
 
+// ---- the send's wire size (hvws_send.hip, hvws_budget.hip) ----
+// header bytes of a frame of n payload bytes (http/websocket_parser.c:189-205)
+__host__ __device__ __forceinline__ uint64_t send_hdr(uint64_t n, uint32_t masked) {
+    return 2u + (n < 126 ? 0u : (n <= 0xFFFFu ? 2u : 8u)) + (masked ? 4u : 0u);
+}
+// Frames and output bytes of one message of len bytes cut into fragments of F
+// (WebSocketChannel.cpp:24-48): all fragments but the last have one size.
+__host__ __device__ __forceinline__ void send_wire(uint64_t len, uint64_t F, uint32_t masked, uint64_t& frames,
+                                                   uint64_t& bytes) {
+    if (len <= F) {
+        frames = 1;
+        bytes = send_hdr(len, masked) + len;
+        return;
+    }
+    frames = (len - 1) / F + 1;
+    const uint64_t last = len - (frames - 1) * F, full = send_hdr(F, masked) + F;
+    // (frames - 1) * full <= 15 * len: saturate where that could wrap
+    bytes = (len >> 59) ? ~0ull : (frames - 1) * full + send_hdr(last, masked) + last;
+}
+
 struct hdr {
     uint64_t length;
     uint32_t hlen;

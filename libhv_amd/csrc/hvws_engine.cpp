@@ -273,7 +273,8 @@ struct pass_replies {
 // deliveries, bad, replies}, the sort's two pair arrays (keys, then values) and
 // its histograms, the delivery table and the reply of each delivery,
 // per-destination first / count.  rep / msg: the reply call (pass_replies::seq)
-// and the message call (pass_msg::seq) it expanded.
+// and the message call (pass_msg::seq) it expanded.  key_in: which of ping /
+// pong holds the sorted keys (hvws_budget reads them).
 struct pass_fan {
     dbuf scan, in, seg, meta, ping, pong, hist, msgs, reply, first, count;
     up_slot up;
@@ -281,9 +282,27 @@ struct pass_fan {
     uint32_t ndest = 0;
     uint64_t n = 0;   // deliveries
     uint64_t rep = 0, msg = 0;
+    int key_in = 0;
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&scan, &in, &seg, &meta, &ping, &pong, &hist, &msgs, &reply, &first, &count});
         up.release(ph);
+    }
+};
+
+// hvws_budget: the size scan's scratch (the wire bytes before each delivery,
+// the scans' scratch), per destination count2 / kept bytes / flags / first2 /
+// byte_off, the kept table and the reply of each kept delivery, {kept
+// deliveries, kept bytes, dropped deliveries, destinations over}.  Nothing
+// per-connection goes up: no slot.  rep / msg: the pass_fan::rep / msg pair of
+// the fan-out it ran over (hvws_fanout clears have), gen: the scans before it.
+struct pass_budget {
+    dbuf scan, cnt, kept, flags, first, off, msgs, reply, meta;
+    bool have = false;
+    uint32_t ndest = 0;
+    uint64_t n = 0;   // the fan-out's deliveries
+    uint64_t rep = 0, msg = 0, gen = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &cnt, &kept, &flags, &first, &off, &msgs, &reply, &meta});
     }
 };
 
@@ -431,6 +450,7 @@ struct hvws_ctx {
     pass_send sd;
     pass_replies rp;
     pass_fan fan;
+    pass_budget bg;
     pass_subs subs;
     pass_check ck;
     pass_tx tx;
@@ -2505,6 +2525,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->sd.release(ph);
         c->rp.release(ph);
         c->fan.release(ph);
+        c->bg.release(ph);
         c->subs.release(ph);
         c->ck.release(ph);
         c->tx.release(ph);
@@ -3844,6 +3865,7 @@ int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_me
     if (rc) return rc;
     if (out_deliveries) *out_deliveries = 0;
     c->fan.have = false;   // the tables are being rewritten
+    c->bg.have = false;    // ... which a budget pass ran over
     if (!c->rp.have || !c->mg.have) return set_err(HVWS_EINVAL, "hvws_fanout without a preceding hvws_replies");
     if (c->rp.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_fanout: a scan has run since hvws_replies");
     if (flags & ~(uint32_t)HVWS_FAN_SELF) return set_err(HVWS_EINVAL, "hvws_fanout: unknown flag bits");
@@ -3908,7 +3930,7 @@ int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_me
     HIP_OR(timed_begin(c), HVWS_EHIP);
     HIP_OR(launch_fan_deliver(t, c->fan.scan.p, nedges, ndel, key, val, c->fan.hist.as<uint64_t>(),
                               c->fan.msgs.as<dtxmsg>(), c->fan.reply.as<uint64_t>(), c->fan.first.as<uint64_t>(),
-                              c->fan.count.as<uint64_t>(), c->stream),
+                              c->fan.count.as<uint64_t>(), &c->fan.key_in, c->stream),
            HVWS_EHIP);
     HIP_OR(timed_end(c), HVWS_EHIP);
     c->fan.have = true;
@@ -3953,6 +3975,103 @@ int hvws_get_dest_fanout(hvws_ctx* c, uint64_t* first, uint64_t* count) {
     if (!fan_valid(c)) return set_err(HVWS_EINVAL, "no hvws_fanout call yet");
     const uint64_t nd = c->fan.ndest;
     return read_rows(c, {{first, c->fan.first.p, nd * 8}, {count, c->fan.count.p, nd * 8}});
+}
+
+static_assert(BF_OVER == HVWS_BF_OVER, "budget flag bits");
+
+// The last hvws_fanout's deliveries cut at every destination's byte budget
+// (hvws_budget.hip): the size scan, the cut, two scans over the destinations,
+// the placement.  No wait: the fan-out's delivery count is on the host already.
+int hvws_budget(hvws_ctx* c, const uint64_t* d_budget, uint64_t budget_all, uint64_t fragment, int masked) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    c->bg.have = false;   // the tables are being rewritten
+    if (!fan_valid(c)) return set_err(HVWS_EINVAL, "hvws_budget without a preceding hvws_fanout");
+    if (c->rp.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_budget: a scan has run since hvws_replies");
+    if (masked != 0 && masked != 1) return set_err(HVWS_EINVAL, "hvws_budget: masked = %d (0 or 1)", masked);
+    const uint64_t n = c->fan.n;
+    const uint32_t ndest = c->fan.ndest;
+    const uint64_t F = fragment ? fragment : 0xFFFFu;   // WebSocketChannel.cpp:6
+    // no row names more than the message call's out_cap bytes: n messages of that
+    // length bound every sum the kernels form
+    const uint64_t maxlen = c->mg.out_cap, wmax = budget_wire(maxlen, F, masked);
+    if (n && (wmax == ~0ull || wmax > ~0ull / n))
+        return set_err(HVWS_EINVAL, "hvws_budget: %llu deliveries of up to %llu bytes do not fit 64 bits",
+                       (unsigned long long)n, (unsigned long long)wmax);
+    pass_budget& p = c->bg;
+    HIP_OR(p.scan.ensure(budget_scratch_words(n, ndest) * 8), HVWS_ENOMEM);
+    HIP_OR(p.cnt.ensure((uint64_t)ndest * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.kept.ensure((uint64_t)ndest * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.flags.ensure((uint64_t)ndest + 16), HVWS_ENOMEM);
+    HIP_OR(p.first.ensure(((uint64_t)ndest + 1) * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.off.ensure(((uint64_t)ndest + 1) * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.msgs.ensure((n + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(p.reply.ensure((n + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
+    const uint32_t* key = (c->fan.key_in ? c->fan.pong : c->fan.ping).as<uint32_t>();
+    const budget_tables t{c->fan.msgs.as<dtxmsg>(), c->fan.reply.as<uint64_t>(), key, n, c->fan.first.as<uint64_t>(),
+                          c->fan.count.as<uint64_t>(), ndest, d_budget, budget_all, F, maxlen, masked != 0};
+    const budget_work w{p.scan.as<uint64_t>(), p.cnt.as<uint64_t>(), p.kept.as<uint64_t>(), p.flags.as<uint8_t>(),
+                        p.first.as<uint64_t>(), p.off.as<uint64_t>(), p.msgs.as<dtxmsg>(), p.reply.as<uint64_t>(),
+                        p.meta.as<uint64_t>()};
+    // the timed device work (hvws_last_kernel_ms): the whole pass
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_budget(t, w, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    p.ndest = ndest;
+    p.n = n;
+    p.rep = c->fan.rep;
+    p.msg = c->fan.msg;
+    p.gen = c->scan_gen;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_budget's tables stand: its fan-out's do, and no scan since.
+bool budget_valid(const hvws_ctx* c) {
+    return fan_valid(c) && c->bg.have && c->bg.rep == c->fan.rep && c->bg.msg == c->fan.msg && c->bg.gen == c->scan_gen;
+}
+}  // namespace
+
+const hvws_tx_msg* hvws_budget_device(hvws_ctx* c) { return budget_valid(c) ? c->bg.msgs.as<hvws_tx_msg>() : nullptr; }
+
+const uint64_t* hvws_budget_count_device(hvws_ctx* c) { return budget_valid(c) ? c->bg.meta.as<uint64_t>() : nullptr; }
+
+int64_t hvws_budget_count(hvws_ctx* c) {
+    if (check_ctx(c)) return -1;
+    if (!budget_valid(c)) {
+        set_err(HVWS_EINVAL, "no hvws_budget call yet");
+        return -1;
+    }
+    return read_count(c, c->bg.meta.as<uint64_t>(), "hvws_budget_count");
+}
+
+int hvws_get_budget(hvws_ctx* c, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n) {
+    const int64_t have = hvws_budget_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first)
+        return set_err(HVWS_EINVAL, "kept delivery range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{out, c->bg.msgs.as<dtxmsg>() + first, n * sizeof(dtxmsg)},
+                         {reply, c->bg.reply.as<uint64_t>() + first, n * 8}});
+}
+
+int hvws_get_dest_budget(hvws_ctx* c, uint64_t* first, uint64_t* count, uint64_t* byte_off, uint8_t* flags) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!budget_valid(c)) return set_err(HVWS_EINVAL, "no hvws_budget call yet");
+    const uint64_t nd = c->bg.ndest;
+    return read_rows(c, {{first, c->bg.first.p, nd * 8},
+                         {count, c->bg.cnt.p, nd * 8},
+                         {byte_off, c->bg.off.p, (nd + 1) * 8},
+                         {flags, c->bg.flags.p, nd}});
+}
+
+int hvws_get_budget_totals(hvws_ctx* c, uint64_t out[4]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!budget_valid(c)) return set_err(HVWS_EINVAL, "no hvws_budget call yet");
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_budget_totals: null out");
+    return read_rows(c, {{out, c->bg.meta.p, 32}});
 }
 
 static_assert(HVWS_SUB_JOIN == 1u && HVWS_SUB_LEAVE == 2u && HVWS_SUB_DROP == 3u && HVWS_SUBS_UNIQUE == 1u &&

@@ -354,7 +354,7 @@ hipError_t launch_fan_sort(uint32_t* const key[2], uint32_t* const val[2], uint6
 
 hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_t nedges, uint64_t ndel, uint32_t* key[2],
                               uint32_t* val[2], uint64_t* hist, dtxmsg* out, uint64_t* reply, uint64_t* first,
-                              uint64_t* count, hipStream_t st) {
+                              uint64_t* count, int* key_in, hipStream_t st) {
     int cur = 0;
     if (nedges) {
         hipLaunchKernelGGL(k_fan_expand, dim3((uint32_t)((nedges + 255) / 256)), dim3(256), 0, st, in,
@@ -368,6 +368,7 @@ hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_
                                out, reply);
     }
     hipLaunchKernelGGL(k_fan_dests, dim3((in.ndest + 255) / 256), dim3(256), 0, st, key[cur], ndel, in.ndest, first, count);
+    *key_in = cur;
     return hipGetLastError();
 }
 

@@ -651,16 +651,59 @@ hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* self
 // Expansion, sort and finish for nedges edges of which ndel are delivered (both
 // read by the host from meta, bad == 0): key / val are the ping-pong pair
 // arrays (nedges words each), hist fan_hist_words(nedges) words; out / reply:
-// ndel entries, first / count: ndest.
+// ndel entries, first / count: ndest.  *key_in: which of key[0], key[1] holds the
+// sorted keys afterwards (its first ndel words are 2 * destination + (opcode == 8)
+// of each delivery; hvws_budget.hip reads them).
 hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_t nedges, uint64_t ndel, uint32_t* key[2],
                               uint32_t* val[2], uint64_t* hist, dtxmsg* out, uint64_t* reply, uint64_t* first,
-                              uint64_t* count, hipStream_t st);
+                              uint64_t* count, int* key_in, hipStream_t st);
 // The sort of launch_fan_deliver on its own: n pairs by the low 8 * passes bits
 // of their keys, stable, between the ping-pong arrays; *cur says which of the
 // two holds the pairs, before and after.  hist: fan_hist_words(n) words.
 uint32_t fan_key_passes(uint64_t max_key);     // ceil(bits(max_key) / 8)
 hipError_t launch_fan_sort(uint32_t* const key[2], uint32_t* const val[2], uint64_t n, uint32_t passes, uint64_t* hist,
                            int* cur, hipStream_t st);
+// hvws_budget (hvws_budget.hip; include/hvws.h has the contract).  What its
+// kernels read: the delivery table of launch_fan_deliver (rows, reply, n of them
+// -- the host knows the count), its sorted keys, first / count per destination,
+// and the caller's budgets (device, ndest words, or null: budget_all for all).
+// F: bytes per fragment; maxlen: the longest message a row can name.
+enum : uint32_t { BF_OVER = 1u };
+struct budget_tables {
+    const dtxmsg* rows;
+    const uint64_t* reply;
+    const uint32_t* key;
+    uint64_t n;
+    const uint64_t* first;
+    const uint64_t* count;
+    uint32_t ndest;
+    const uint64_t* budget;
+    uint64_t budget_all;
+    uint64_t F, maxlen;
+    bool masked;
+};
+// What they write: scratch (budget_scratch_words(n, ndest) words: the wire bytes
+// before each delivery, their total, the scans' scratch), count2 / kept / flags
+// per destination (kept: its kept wire bytes), first2 and byte_off (ndest + 1
+// words each, the totals last), out / reply_out (n entries), meta (8 words):
+// [0..3] = kept deliveries, kept bytes, dropped deliveries, destinations over.
+struct budget_work {
+    uint64_t* scratch;
+    uint64_t* count2;
+    uint64_t* kept;
+    uint8_t* flags;
+    uint64_t* first2;
+    uint64_t* byte_off;
+    dtxmsg* out;
+    uint64_t* reply_out;
+    uint64_t* meta;
+};
+uint64_t budget_scratch_words(uint64_t n, uint32_t ndest);
+// The bytes the send emits for a message of len bytes (saturating): on the host,
+// for the bound hvws_budget checks before it launches.
+uint64_t budget_wire(uint64_t len, uint64_t F, int masked);
+// The whole pass, no wait.  No read leaves budget[0 .. ndest).
+hipError_t launch_budget(const budget_tables& t, const budget_work& w, hipStream_t st);
 // hvws_subs_update (hvws_subs.hip; include/hvws.h has the contract).  dsubev
 // mirrors hvws_sub_event.  What its kernels read: the caller's table, the
 // events and dest_of (device copies; dest_of null: no implicit drops) and the

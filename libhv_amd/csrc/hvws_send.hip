@@ -65,11 +65,6 @@ static_assert(frag_key(0x12345678u, 1) == 0x047660EAu && frag_key(0x12345678u, 2
                   frag_key(0, 1) == 0x92CA2F0Eu && frag_key(0xFFFFFFFFu, 0xFFFFFFFFu) == 0x3B66B2AAu,
               "frag_key: the known answers of include/hvws.h");
 
-// header bytes of a frame of n payload bytes (http/websocket_parser.c:189-205)
-__device__ __forceinline__ uint64_t send_hdr(uint64_t n, uint32_t masked) {
-    return 2u + (n < 126 ? 0u : (n <= 0xFFFFu ? 2u : 8u)) + (masked ? 4u : 0u);
-}
-
 // What message i adds to the scan.  Messages at or beyond the effective count
 // (min(*n_dev, n); n_dev may be null) add the identity.
 struct send_load {
@@ -86,11 +81,8 @@ struct send_load {
         if (i >= count()) return snd3{};
         const dtxmsg m = msgs[i];
         if (m.off > plen || m.len > plen - m.off || (m.flags & ~0x1Fu)) return snd3{0, 0, 1};
-        if (m.len <= F) return snd3{1, send_hdr(m.len, masked) + m.len, 0};
-        const uint64_t fr = (m.len - 1) / F + 1, last = m.len - (fr - 1) * F;
-        const uint64_t full = send_hdr(F, masked) + F;
-        // (fr - 1) * full <= 15 * len: saturate where that could wrap
-        const uint64_t bytes = (m.len >> 59) ? ~0ull : (fr - 1) * full + send_hdr(last, masked) + last;
+        uint64_t fr, bytes;
+        send_wire(m.len, F, masked, fr, bytes);   // hvws_dev.h
         return snd3{fr, bytes, 0};
     }
 };
