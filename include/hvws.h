@@ -44,6 +44,11 @@
  *   hvws_budget  hio_write's over-limit rule (event/nio.c:554-560) for that
  *                table: every destination's deliveries cut at its byte budget,
  *                the destinations that went over, each one's byte range.
+ *   hvws_route   what a pub/sub server's onmessage does first (user code in the
+ *                reference): each data message's command header read on the
+ *                device -- publish to a topic, subscribe, unsubscribe -- into a
+ *                topic per reply for hvws_fanout_routed and the join / leave
+ *                events for hvws_subs_update.
  *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -1011,6 +1016,120 @@ const uint64_t* hvws_fanout_count_device(hvws_ctx* ctx);
 int64_t hvws_fanout_count(hvws_ctx* ctx);
 int hvws_get_fanout(hvws_ctx* ctx, hvws_tx_msg* out, uint64_t* reply, uint64_t first, uint64_t n);
 int hvws_get_dest_fanout(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+
+/* ---- per-message topics and subscribe commands, device resident ------------- */
+/* hvws_fanout takes one topic per connection for the whole batch, and
+ * hvws_subs_update takes the joins and leaves from the host.  Where the clients
+ * choose their topics -- a message names its room, "subscribe me to room 7"
+ * arrives as a WebSocket message -- both need the message bytes, which are on
+ * the device.  hvws_route reads the first bytes of every TEXT / BINARY reply of
+ * the last hvws_replies / hvws_replies_checked where the message call left them
+ * and leaves on the device a topic per REPLY, the reply rows with the command
+ * header trimmed off, and the dense list of join / leave events;
+ * hvws_fanout_routed is hvws_fanout reading those.  The reference has no
+ * counterpart: its onmessage is user code.
+ *
+ * The command header.  A routed message, TEXT or BINARY alike, begins with one
+ * header line of at most HVWS_ROUTE_HDR_MAX = 12 bytes:
+ *     header = verb digits LF
+ *     verb   = 'P' (0x50) | 'S' (0x53) | 'U' (0x55)
+ *     digits = "0" | [1-9][0-9]{0,9}     decimal topic id, no sign, no leading zero
+ *     LF     = 0x0A
+ * With L the message length and h the header length (3 .. 12):
+ *   - 'P': a publication to that topic.  The body is bytes [h, L) and may be
+ *     empty; what is delivered is the body alone, with the reply's opcode and
+ *     FIN (an ASCII line taken off the front of a valid UTF-8 text leaves it
+ *     valid).
+ *   - 'S' / 'U': subscribe / unsubscribe the sender; L must equal h.
+ *   - everything else is malformed: L == 0; another verb (lowercase included);
+ *     no digit; a leading zero; an eleventh digit; no LF within the first 12
+ *     bytes or before the message ends ("P1\r\n" is malformed); a value >=
+ *     ntopics, compared in 64 bits (ten digits exceed 2^32); 'S' / 'U' with
+ *     bytes behind the LF.
+ * Topic names instead of numbers (a hash table on the device) are out of scope:
+ * names are the host's, numeric ids the device's.
+ *
+ * The rule, over the reply table R[0 .. nr) in table order, s_i the segment of
+ * the piece reply i answers:
+ *   - opcode other than 1 / 2 (PONG, CLOSE): kind HVWS_RK_OTHER, the row
+ *     unchanged, topic HVWS_FAN_NONE.
+ *   - opcode 1 / 2, parsed as above.  HVWS_RK_PUB: the row has off += h,
+ *     len -= h, flags and key unchanged, topic[i] = the id.  HVWS_RK_SUB,
+ *     HVWS_RK_UNSUB, HVWS_RK_BAD: the row unchanged, topic HVWS_FAN_NONE.
+ *   - a malformed message fails its connection for this pass.  With b[s] the
+ *     smallest reply index of kind BAD in segment s, every opcode-1 / 2 reply of
+ *     s with index > b[s] has kind HVWS_RK_STOPPED whatever it holds (row
+ *     unchanged, topic HVWS_FAN_NONE).  Neither BAD nor STOPPED replies deliver
+ *     or produce an event; PONG and CLOSE replies of s are untouched (they are
+ *     the reply call's business).  flags[s] gets HVWS_RT_BAD and bad_reply[s] =
+ *     b[s], HVWS_ROUTE_NONE without one.  The host closes the connection (with
+ *     1008, or what it likes) and passes it to hvws_subs_update as a DROP.  In
+ *     the RFC form a connection's data replies are in stream order, so b[s] is
+ *     its first malformed message in the stream.
+ *   - events: a dense table, one hvws_sub_event per SUB (HVWS_SUB_JOIN) and
+ *     UNSUB (HVWS_SUB_LEAVE) reply, in reply order, {op, topic, dest_of[s_i]}:
+ *     the array order hvws_subs_update applies.  A subscription therefore takes
+ *     effect in the next turn's table, as that call documents.
+ * The outputs are functions of the input alone: the same on every run, whatever
+ * the kernels' geometry.
+ *
+ * hvws_route runs after hvws_replies / hvws_replies_checked, behind any of the
+ * three message forms, is asynchronous on the ctx stream and does not wait;
+ * hvws_last_kernel_ms reports it when it was the last call.  dest_of: host, nseg
+ * words, segment s's own destination id.  It writes nothing the reply, message,
+ * check or fan-out getters read: a plain hvws_fanout after it works on the
+ * untouched reply table.  HVWS_EINVAL, nothing launched: no preceding reply
+ * call, or a scan since it; dest_of NULL or an entry >= ndest; ndest 0 or above
+ * 2^31 - 1; a reply capacity >= 2^32 - 1.  The message bytes are those of the
+ * message call's d_out, which must still hold that call's output; no read
+ * leaves [off, off + min(len, 12)) of a reply, nor [0, out_cap).  A deferred
+ * piece is not in R and so is not routed.  The results are valid until the next
+ * hvws_route, reply call, message call or scan on ctx; every getter reports
+ * none after that (the _device ones NULL, hvws_route_event_count -1, the others
+ * HVWS_EINVAL).  hvws_route_device: the routed rows, one per reply;
+ * hvws_route_topics_device: the topic per reply; hvws_route_events_device /
+ * hvws_route_event_count_device: the event table and its count.  These four do
+ * not wait; the others do.  hvws_get_route: replies first .. first + n - 1, any
+ * pointer may be NULL, a range beyond the reply count is HVWS_EINVAL;
+ * hvws_get_route_events likewise over the events (what hvws_subs_update takes
+ * as its host array: 12 B per event); hvws_get_route_flags: nseg entries each,
+ * either may be NULL; hvws_get_route_totals: publications, subscribes,
+ * unsubscribes, bad + stopped.
+ *
+ * hvws_fanout_routed follows hvws_fanout's contract word for word, except:
+ * reply i's topic is topic[i] of the valid hvws_route on ctx, not pub[s_i]; the
+ * rows delivered are the routed rows; ntopics, ndest and dest_of are that route
+ * call's (none valid: HVWS_EINVAL); and since only the device knows which
+ * replies publish, a NULL subscription table is refused whenever ntopics != 0.
+ * A publication has one edge per listing of its topic, the self edge dropped
+ * unless HVWS_FAN_SELF is set, a destination listed twice delivered twice;
+ * PONG and CLOSE take one edge to the sender; SUB, UNSUB, BAD and STOPPED
+ * replies have no edge; the sort key is (destination, op == 8, i, j); there is
+ * one wait; the rules for bad rows and member ids apply only where a
+ * publication reaches them.  It fills hvws_fanout's tables: every fan-out
+ * getter (reply[k] is still the reply index), hvws_budget and
+ * hvws_send_messages run behind it unchanged.   */
+#define HVWS_ROUTE_HDR_MAX 12u
+#define HVWS_RK_OTHER   0u   /* PONG, CLOSE: not parsed */
+#define HVWS_RK_PUB     1u
+#define HVWS_RK_SUB     2u
+#define HVWS_RK_UNSUB   3u
+#define HVWS_RK_BAD     4u   /* malformed */
+#define HVWS_RK_STOPPED 5u   /* a data reply behind its connection's first malformed one */
+#define HVWS_RT_BAD     1u   /* flags[s]: the connection sent a malformed message */
+#define HVWS_ROUTE_NONE UINT64_MAX
+int hvws_route(hvws_ctx* ctx, uint32_t ntopics, uint32_t ndest, const uint32_t* dest_of);
+const hvws_tx_msg* hvws_route_device(hvws_ctx* ctx);
+const uint32_t* hvws_route_topics_device(hvws_ctx* ctx);
+const struct hvws_sub_event* hvws_route_events_device(hvws_ctx* ctx);
+const uint64_t* hvws_route_event_count_device(hvws_ctx* ctx);
+int hvws_get_route(hvws_ctx* ctx, hvws_tx_msg* rows, uint32_t* topic, uint8_t* kind, uint64_t first, uint64_t n);
+int64_t hvws_route_event_count(hvws_ctx* ctx);
+int hvws_get_route_events(hvws_ctx* ctx, struct hvws_sub_event* out, uint64_t first, uint64_t n);
+int hvws_get_route_flags(hvws_ctx* ctx, uint8_t* flags, uint64_t* bad_reply);
+int hvws_get_route_totals(hvws_ctx* ctx, uint64_t out[4]);
+int hvws_fanout_routed(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                       uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries);
 
 /* ---- per-destination write limits for the fan-out, device resident ---------- */
 /* hvws_budget cuts every destination's deliveries of the last hvws_fanout at

@@ -103,6 +103,11 @@ SUB_JOIN, SUB_LEAVE, SUB_DROP = 1, 2, 3
 SUBS_UNIQUE = 1
 SUB_EVENT_DTYPE = np.dtype([("op", "<u4"), ("topic", "<u4"), ("dest", "<u4")])
 assert SUB_EVENT_DTYPE.itemsize == 12
+# HVWS_ROUTE_*, HVWS_RK_* and HVWS_RT_BAD (hvws_route)
+ROUTE_HDR_MAX = 12
+RK_OTHER, RK_PUB, RK_SUB, RK_UNSUB, RK_BAD, RK_STOPPED = 0, 1, 2, 3, 4, 5
+RT_BAD = 1
+ROUTE_NONE = (1 << 64) - 1
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -244,6 +249,24 @@ _SIGS = {
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     ),
     "hvws_get_dest_fanout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
+    "hvws_route_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_route_topics_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_route_events_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_route_event_count_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_get_route": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64],
+    ),
+    "hvws_route_event_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_route_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "hvws_get_route_flags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_get_route_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_fanout_routed": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+         ctypes.POINTER(ctypes.c_uint64)],
+    ),
     "hvws_budget": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
     ),
@@ -823,6 +846,67 @@ class Engine:
         cnt = np.zeros(max(ndest, 1), np.uint64)
         _check(lib().hvws_get_dest_fanout(self.ctx, first.ctypes.data, cnt.ctypes.data), "hvws_get_dest_fanout")
         return first[:ndest], cnt[:ndest]
+
+    def route(self, ntopics: int, ndest: int, dest_of) -> None:
+        """hvws_route over the last replies() / replies_checked() call: every TEXT /
+        BINARY reply classified by its command header ('P' / 'S' / 'U', a decimal
+        topic id, LF) into a topic per reply, the rows with the header trimmed off
+        and the join / leave events.  dest_of: each segment's own destination id.
+        No wait."""
+        do = np.ascontiguousarray(dest_of, dtype=np.uint32) if dest_of is not None else None
+        _check(lib().hvws_route(self.ctx, ntopics, ndest, do.ctypes.data if do is not None else None), "hvws_route")
+
+    def route_table(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(routed rows [TX_MSG_DTYPE], topic, kind RK_*) per reply of the last route() call."""
+        L = lib()
+        if not L.hvws_route_device(self.ctx):
+            _check(-2, "hvws_get_route")
+        n = L.hvws_reply_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_reply_count")
+        rows = np.zeros(n, dtype=TX_MSG_DTYPE)
+        topic = np.zeros(n, dtype=np.uint32)
+        kind = np.zeros(n, dtype=np.uint8)
+        _check(L.hvws_get_route(self.ctx, rows.ctypes.data, topic.ctypes.data, kind.ctypes.data, 0, n), "hvws_get_route")
+        return rows, topic, kind
+
+    def route_events(self) -> np.ndarray:
+        """The join / leave events [SUB_EVENT_DTYPE] of the last route() call, in
+        reply order: the events argument of subs_update()."""
+        n = lib().hvws_route_event_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_route_event_count")
+        out = np.zeros(n, dtype=SUB_EVENT_DTYPE)
+        _check(lib().hvws_get_route_events(self.ctx, out.ctypes.data, 0, n), "hvws_get_route_events")
+        return out
+
+    def route_flags(self, nseg: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(RT_* flags, first malformed reply or ROUTE_NONE) per segment of the last route() call."""
+        flags = np.zeros(max(nseg, 1), np.uint8)
+        bad = np.zeros(max(nseg, 1), np.uint64)
+        _check(lib().hvws_get_route_flags(self.ctx, flags.ctypes.data, bad.ctypes.data), "hvws_get_route_flags")
+        return flags[:nseg], bad[:nseg]
+
+    def route_totals(self) -> Tuple[int, int, int, int]:
+        """(publications, subscribes, unsubscribes, bad + stopped) of the last route() call."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hvws_get_route_totals(self.ctx, out), "hvws_get_route_totals")
+        return tuple(int(x) for x in out)
+
+    def fanout_routed(self, topic_first, member, nmember: int, flags: int = 0,
+                      max_deliveries: int = (1 << 64) - 1) -> int:
+        """hvws_fanout_routed: fanout() with the topic per reply, the rows, ntopics,
+        ndest and dest_of of the last route() call.  Returns the deliveries;
+        last_deliveries holds them even when the call fails for max_deliveries.
+        fanout_table(), dest_fanout(), budget() and send_messages() follow as
+        they follow fanout()."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        n = ctypes.c_uint64(0)
+        rc = lib().hvws_fanout_routed(self.ctx, dev(topic_first), dev(member), nmember, flags, max_deliveries,
+                                      ctypes.byref(n))
+        self.last_deliveries = int(n.value)
+        _check(rc, "hvws_fanout_routed")
+        return int(n.value)
 
     def budget(self, budget, budget_all: int = (1 << 64) - 1, fragment: int = 0, masked: bool = False) -> None:
         """hvws_budget over the last fanout() call: every destination's deliveries

@@ -289,6 +289,24 @@ struct pass_fan {
     }
 };
 
+// hvws_route: the count scan's scratch, dest_of per segment (it goes up through
+// the slot), the routed rows, topic and kind per reply, bad_reply and flags per
+// segment, the event table, {events, publications, subscribes, unsubscribes,
+// bad + stopped}.  rep / msg / gen: the reply call, the message call and the
+// scans it ran behind; ntopics / ndest: its arguments (hvws_fanout_routed
+// takes them from here).
+struct pass_route {
+    dbuf scan, in, rows, topic, kind, bad, flags, ev, meta;
+    up_slot up;
+    bool have = false;
+    uint32_t nseg = 0, ntopics = 0, ndest = 0;
+    uint64_t rep = 0, msg = 0, gen = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &in, &rows, &topic, &kind, &bad, &flags, &ev, &meta});
+        up.release(ph);
+    }
+};
+
 // hvws_budget: the size scan's scratch (the wire bytes before each delivery,
 // the scans' scratch), per destination count2 / kept bytes / flags / first2 /
 // byte_off, the kept table and the reply of each kept delivery, {kept
@@ -450,6 +468,7 @@ struct hvws_ctx {
     pass_send sd;
     pass_replies rp;
     pass_fan fan;
+    pass_route rt;
     pass_budget bg;
     pass_subs subs;
     pass_check ck;
@@ -2525,6 +2544,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->sd.release(ph);
         c->rp.release(ph);
         c->fan.release(ph);
+        c->rt.release(ph);
         c->bg.release(ph);
         c->subs.release(ph);
         c->ck.release(ph);
@@ -3855,6 +3875,11 @@ int hvws_get_reply_flags(hvws_ctx* c, uint8_t* out) {
 
 static_assert(HVWS_FAN_NONE == 0xFFFFFFFFu && HVWS_FAN_SELF == 1u, "fanout constants");
 
+namespace {
+int fan_run(hvws_ctx* c, const char* who, const fan_tables& t, uint64_t per, uint64_t max_deliveries,
+            uint64_t* out_deliveries);
+}
+
 // The last reply call's table through a subscription table, ordered by
 // destination (hvws_fan.hip): the edge count, one wait for {edges, deliveries,
 // bad}, then expansion, sort and finish.
@@ -3888,10 +3913,7 @@ int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_me
     const uint64_t cap = c->rp.cap;
     // every reply and every edge has a 32-bit index
     if (cap >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "hvws_fanout: %llu replies (max 2^32-2)", (unsigned long long)cap);
-    HIP_OR(c->fan.scan.ensure(fan_scratch_bytes(cap)), HVWS_ENOMEM);
     HIP_OR(c->fan.in.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(c->fan.seg.ensure((uint64_t)nseg * 16 + 16), HVWS_ENOMEM);
-    HIP_OR(c->fan.meta.ensure(64), HVWS_ENOMEM);
     // dest_of, then pub behind it
     if ((rc = c->fan.up.send(c->fan.in.p, c->stream, dest_of, (uint64_t)nseg * 4, publishes ? pub : nullptr,
                              publishes ? (uint64_t)nseg * 4 : 0)) != HVWS_OK)
@@ -3900,23 +3922,37 @@ int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_me
                        c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), c->mg.cap, nseg, c->fan.in.as<uint32_t>(),
                        publishes ? c->fan.in.as<uint32_t>() + nseg : nullptr, d_topic_first, d_member, ntopics, nmember,
                        ndest, (flags & HVWS_FAN_SELF) != 0};
+    return fan_run(c, "hvws_fanout", t, nseg, max_deliveries, out_deliveries);
+}
+
+namespace {
+// What hvws_fanout and hvws_fanout_routed share once their tables stand: the
+// edge count, the one wait, then expansion, sort and finish.  per: the self
+// counts and bad marks the count keeps (one per segment; routed: per reply).
+int fan_run(hvws_ctx* c, const char* who, const fan_tables& t, uint64_t per, uint64_t max_deliveries,
+            uint64_t* out_deliveries) {
+    int rc;
+    const uint32_t ndest = t.ndest;
+    HIP_OR(c->fan.scan.ensure(fan_scratch_bytes(t.rep_cap)), HVWS_ENOMEM);
+    HIP_OR(c->fan.seg.ensure(per * 16 + 16), HVWS_ENOMEM);
+    HIP_OR(c->fan.meta.ensure(64), HVWS_ENOMEM);
     uint64_t* selfc = c->fan.seg.as<uint64_t>();
-    uint32_t* mark = reinterpret_cast<uint32_t*>(selfc + nseg);
+    uint32_t* mark = reinterpret_cast<uint32_t*>(selfc + per);
     uint64_t* meta = c->fan.meta.as<uint64_t>();
-    HIP_OR(launch_fan_count(t, mark, selfc, mark + nseg, c->fan.scan.p, meta, c->stream), HVWS_EHIP);
+    HIP_OR(launch_fan_count(t, mark, selfc, mark + per, c->fan.scan.p, meta, c->stream), HVWS_EHIP);
     // the one wait: [0] edges before the self drop, [1] deliveries, [2] bad replies, [3] replies
     uint64_t h[4] = {0, 0, 0, 0};
     if ((rc = read_rows(c, {{h, meta, sizeof h}})) != HVWS_OK) return rc;
     const uint64_t nedges = h[0], ndel = h[1];
     if (out_deliveries) *out_deliveries = ndel;
     if (h[2])
-        return set_err(HVWS_EINVAL, "hvws_fanout: %llu publications reach a topic row outside the member table or a "
-                       "member id outside the destinations", (unsigned long long)h[2]);
+        return set_err(HVWS_EINVAL, "%s: %llu publications reach a topic row outside the member table or a "
+                       "member id outside the destinations", who, (unsigned long long)h[2]);
     if (ndel > max_deliveries)
-        return set_err(HVWS_EINVAL, "hvws_fanout: %llu deliveries, max_deliveries %llu", (unsigned long long)ndel,
+        return set_err(HVWS_EINVAL, "%s: %llu deliveries, max_deliveries %llu", who, (unsigned long long)ndel,
                        (unsigned long long)max_deliveries);
     if (nedges > 0xFFFFFFFEull)
-        return set_err(HVWS_EINVAL, "hvws_fanout: %llu edges (max 2^32-2)", (unsigned long long)nedges);
+        return set_err(HVWS_EINVAL, "%s: %llu edges (max 2^32-2)", who, (unsigned long long)nedges);
     HIP_OR(c->fan.ping.ensure(nedges * 8 + 16), HVWS_ENOMEM);
     HIP_OR(c->fan.pong.ensure(nedges * 8 + 16), HVWS_ENOMEM);
     HIP_OR(c->fan.hist.ensure(fan_hist_words(nedges) * 8), HVWS_ENOMEM);
@@ -3941,7 +3977,6 @@ int hvws_fanout(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_me
     return HVWS_OK;
 }
 
-namespace {
 // The last hvws_fanout's tables stand: no reply or message call since.
 bool fan_valid(const hvws_ctx* c) {
     return c && c->fan.have && c->rp.have && c->fan.rep == c->rp.seq && c->fan.msg == c->mg.seq;
@@ -3975,6 +4010,136 @@ int hvws_get_dest_fanout(hvws_ctx* c, uint64_t* first, uint64_t* count) {
     if (!fan_valid(c)) return set_err(HVWS_EINVAL, "no hvws_fanout call yet");
     const uint64_t nd = c->fan.ndest;
     return read_rows(c, {{first, c->fan.first.p, nd * 8}, {count, c->fan.count.p, nd * 8}});
+}
+
+static_assert(RK_OTHER == HVWS_RK_OTHER && RK_PUB == HVWS_RK_PUB && RK_SUB == HVWS_RK_SUB && RK_UNSUB == HVWS_RK_UNSUB &&
+                  RK_BAD == HVWS_RK_BAD && RK_STOPPED == HVWS_RK_STOPPED && RT_BAD == HVWS_RT_BAD &&
+                  HVWS_ROUTE_HDR_MAX == 12 && HVWS_ROUTE_NONE == ~0ull,
+              "route constants");
+
+// The last reply call's TEXT / BINARY replies classified by their command
+// header (hvws_route.hip): the parse, one scan, the finish.  No wait.
+int hvws_route(hvws_ctx* c, uint32_t ntopics, uint32_t ndest, const uint32_t* dest_of) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    pass_route& p = c->rt;
+    p.have = false;   // the tables are being rewritten
+    if (!c->rp.have || !c->mg.have) return set_err(HVWS_EINVAL, "hvws_route without a preceding hvws_replies");
+    if (c->rp.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_route: a scan has run since hvws_replies");
+    if (!dest_of) return set_err(HVWS_EINVAL, "hvws_route: null dest_of");
+    if (ndest == 0 || ndest > 0x7FFFFFFFu) return set_err(HVWS_EINVAL, "hvws_route: %u destinations (1 .. 2^31-1)", ndest);
+    const uint32_t nseg = c->rp.nseg;
+    for (uint32_t s = 0; s < nseg; ++s)
+        if (dest_of[s] >= ndest)
+            return set_err(HVWS_EINVAL, "hvws_route: dest_of[%u] = %u of %u destinations", s, dest_of[s], ndest);
+    const uint64_t cap = c->rp.cap;
+    // every reply has a 32-bit index
+    if (cap >= 0xFFFFFFFFull) return set_err(HVWS_EINVAL, "hvws_route: %llu replies (max 2^32-2)", (unsigned long long)cap);
+    HIP_OR(p.scan.ensure(route_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(p.in.ensure((uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.rows.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(p.topic.ensure((cap + 1) * 4), HVWS_ENOMEM);
+    HIP_OR(p.kind.ensure(cap + 16), HVWS_ENOMEM);
+    HIP_OR(p.bad.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.flags.ensure((uint64_t)nseg + 16), HVWS_ENOMEM);
+    HIP_OR(p.ev.ensure((cap + 1) * sizeof(dsubev)), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
+    if ((rc = p.up.send(p.in.p, c->stream, dest_of, (uint64_t)nseg * 4)) != HVWS_OK) return rc;
+    const route_tables t{c->rp.msgs.as<dtxmsg>(), c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap,
+                         c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), c->mg.cap, nseg, p.in.as<uint32_t>(), ntopics,
+                         c->mg.dout, c->mg.dout ? c->mg.out_cap : 0};
+    const route_work w{p.rows.as<dtxmsg>(), p.topic.as<uint32_t>(), p.kind.as<uint8_t>(), p.bad.as<uint64_t>(),
+                       p.flags.as<uint8_t>(), p.ev.as<dsubev>(), p.scan.p, p.meta.as<uint64_t>()};
+    // the timed device work (hvws_last_kernel_ms): the whole pass
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_route(t, w, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    p.nseg = nseg;
+    p.ntopics = ntopics;
+    p.ndest = ndest;
+    p.rep = c->rp.seq;
+    p.msg = c->mg.seq;
+    p.gen = c->scan_gen;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_route's tables stand: no reply call, message call or scan since.
+bool route_valid(const hvws_ctx* c) {
+    return c && c->rt.have && c->rp.have && c->rt.rep == c->rp.seq && c->rt.msg == c->mg.seq && c->rt.gen == c->scan_gen;
+}
+int route_ctx(hvws_ctx* c) {
+    if (int rc = check_ctx(c)) return rc;
+    return route_valid(c) ? HVWS_OK : set_err(HVWS_EINVAL, "no hvws_route call yet");
+}
+}  // namespace
+
+const hvws_tx_msg* hvws_route_device(hvws_ctx* c) { return route_valid(c) ? c->rt.rows.as<hvws_tx_msg>() : nullptr; }
+
+const uint32_t* hvws_route_topics_device(hvws_ctx* c) { return route_valid(c) ? c->rt.topic.as<uint32_t>() : nullptr; }
+
+const hvws_sub_event* hvws_route_events_device(hvws_ctx* c) {
+    return route_valid(c) ? c->rt.ev.as<hvws_sub_event>() : nullptr;
+}
+
+const uint64_t* hvws_route_event_count_device(hvws_ctx* c) { return route_valid(c) ? c->rt.meta.as<uint64_t>() : nullptr; }
+
+int hvws_get_route(hvws_ctx* c, hvws_tx_msg* rows, uint32_t* topic, uint8_t* kind, uint64_t first, uint64_t n) {
+    if (int rc = route_ctx(c)) return rc;
+    const int64_t have = hvws_reply_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "reply range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{rows, c->rt.rows.as<dtxmsg>() + first, n * sizeof(dtxmsg)},
+                         {topic, c->rt.topic.as<uint32_t>() + first, n * 4},
+                         {kind, c->rt.kind.as<uint8_t>() + first, n}});
+}
+
+int64_t hvws_route_event_count(hvws_ctx* c) {
+    if (route_ctx(c)) return -1;
+    return read_count(c, c->rt.meta.as<uint64_t>(), "hvws_route_event_count");
+}
+
+int hvws_get_route_events(hvws_ctx* c, hvws_sub_event* out, uint64_t first, uint64_t n) {
+    const int64_t have = hvws_route_event_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "event range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{out, c->rt.ev.as<dsubev>() + first, n * sizeof(dsubev)}});
+}
+
+int hvws_get_route_flags(hvws_ctx* c, uint8_t* flags, uint64_t* bad_reply) {
+    if (int rc = route_ctx(c)) return rc;
+    const uint64_t nseg = c->rt.nseg;
+    return read_rows(c, {{flags, c->rt.flags.p, nseg}, {bad_reply, c->rt.bad.p, nseg * 8}});
+}
+
+int hvws_get_route_totals(hvws_ctx* c, uint64_t out[4]) {
+    if (int rc = route_ctx(c)) return rc;
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_route_totals: null out");
+    return read_rows(c, {{out, c->rt.meta.as<uint64_t>() + 1, 32}});
+}
+
+// hvws_fanout with the topic per reply and the rows of the last hvws_route.
+int hvws_fanout_routed(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                       uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_deliveries) *out_deliveries = 0;
+    c->fan.have = false;   // the tables are being rewritten
+    c->bg.have = false;    // ... which a budget pass ran over
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_fanout_routed without a preceding hvws_route");
+    if (flags & ~(uint32_t)HVWS_FAN_SELF) return set_err(HVWS_EINVAL, "hvws_fanout_routed: unknown flag bits");
+    // which replies publish is known on the device alone: with a topic to publish to, the table must be there
+    if (c->rt.ntopics && (!d_topic_first || (!d_member && nmember)))
+        return set_err(HVWS_EINVAL, "hvws_fanout_routed: null subscription table");
+    const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
+    const fan_tables t{c->rt.rows.as<dtxmsg>(), c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap,
+                       c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), c->mg.cap, c->rt.nseg, c->rt.in.as<uint32_t>(),
+                       nullptr, d_topic_first, d_member, c->rt.ntopics, nmember, c->rt.ndest,
+                       (flags & HVWS_FAN_SELF) != 0, c->rt.topic.as<uint32_t>()};
+    return fan_run(c, "hvws_fanout_routed", t, cap, max_deliveries, out_deliveries);
 }
 
 static_assert(BF_OVER == HVWS_BF_OVER, "budget flag bits");

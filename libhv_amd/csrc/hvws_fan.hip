@@ -12,7 +12,11 @@
 //                    device-wide scan over the replies (the scan of hvws_dev.h)
 //                    carries {edges, deliveries, bad}: edges before the self drop
 //                    (what the expansion and the sort run over), deliveries after
-//                    it (what the host waits for), all saturating.
+//                    it (what the host waits for), all saturating.  In the
+//                    routed form (hvws_fanout_routed: a topic per reply from
+//                    hvws_route) each publication may reach another row, so the
+//                    walk is per publishing reply, one wavefront each: its work
+//                    is the edge count, the order of the expansion's.
 //   the expansion    one thread per EDGE: edge e finds its reply by binary search
 //                    over the scan and writes the pair (key, reply), key =
 //                    2 * destination + (opcode == 8).  A dropped self edge gets
@@ -74,6 +78,15 @@ __device__ __forceinline__ uint32_t fan_topic(const fan_tables& t, uint32_t s) {
     const uint32_t tp = t.pub[s];
     return tp < t.ntopics ? tp : FAN_NONE;   // the host refused any other value but NONE
 }
+// The topic of reply i of segment s, and where its self count and bad mark
+// stand: per segment, or per reply in the routed form (hvws_fanout_routed),
+// where a reply's topic is hvws_route's.
+__device__ __forceinline__ uint32_t fan_topic_of(const fan_tables& t, uint64_t i, uint32_t s) {
+    if (!t.rtopic) return fan_topic(t, s);
+    const uint32_t tp = t.rtopic[i];
+    return tp < t.ntopics ? tp : FAN_NONE;
+}
+__device__ __forceinline__ uint64_t fan_slot(const fan_tables& t, uint64_t i, uint32_t s) { return t.rtopic ? i : s; }
 // topic tp's row, true when it lies inside the member table
 __device__ __forceinline__ bool fan_row(const fan_tables& t, uint32_t tp, uint64_t& a, uint64_t& b) {
     a = t.topic_first[tp];
@@ -138,6 +151,42 @@ __global__ __launch_bounds__(256) void k_fan_self(fan_tables in, const uint32_t*
     }
 }
 
+// The routed form: one wavefront per publishing reply walks that reply's topic
+// row once: selfc[i] = listings of the sender's own destination, repbad[i] = 1
+// for a row outside the member table or a member id outside [0, ndest).  The
+// work is the edge count, as the expansion's.  Other replies read and write
+// nothing: fan_load does not look at their words.
+__global__ __launch_bounds__(256) void k_fan_self_reply(fan_tables in, uint64_t* __restrict__ selfc,
+                                                        uint32_t* __restrict__ repbad) {
+    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x / 64u) + (threadIdx.x >> 6);   // uniform over the wave
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= fan_replies(in)) return;
+    if (!is_pub(in.rep[i].flags)) return;
+    const uint32_t s = fan_seg(in, i);
+    if (s >= in.nseg) return;
+    const uint32_t tp = fan_topic_of(in, i, s);
+    if (tp == FAN_NONE) return;
+    uint64_t a, b, n = 0;
+    uint32_t bad = 0;
+    if (!fan_row(in, tp, a, b)) {
+        bad = 1u;
+    } else {
+        const uint32_t me = in.dest_of[s];
+        for (uint64_t k = a + lane; k < b; k += 64) {
+            const uint32_t d = in.member[k];
+            n += d == me ? 1u : 0u;
+            bad |= d >= in.ndest ? 1u : 0u;
+        }
+    }
+    const uint64_t mb = __ballot(bad != 0);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) n += __shfl_down(n, o);
+    if (lane == 0) {
+        selfc[i] = n;
+        repbad[i] = mb ? 1u : 0u;
+    }
+}
+
 // What reply i adds to the scan.  Replies at or beyond the count add the identity.
 struct fan_load {
     fan_tables in;
@@ -148,12 +197,13 @@ struct fan_load {
         const uint32_t s = fan_seg(in, i);
         if (s >= in.nseg) return fan3{0, 0, 1};
         if (!is_pub(in.rep[i].flags)) return fan3{1, 1, 0};   // PONG, CLOSE: to the sender alone
-        const uint32_t tp = fan_topic(in, s);
+        const uint32_t tp = fan_topic_of(in, i, s);
         if (tp == FAN_NONE) return fan3{};
-        if (segbad[s]) return fan3{0, 0, 1};
+        const uint64_t x = fan_slot(in, i, s);
+        if (segbad[x]) return fan3{0, 0, 1};
         uint64_t a, b;
         fan_row(in, tp, a, b);
-        const uint64_t e = b - a, own = in.self ? 0 : selfc[s];
+        const uint64_t e = b - a, own = in.self ? 0 : selfc[x];
         return fan3{e, e - own, 0};
     }
 };
@@ -188,7 +238,7 @@ __global__ __launch_bounds__(256) void k_fan_expand(fan_tables in, const fan3* _
     uint32_t k;
     if (is_pub(fl)) {
         uint64_t a, b;
-        fan_row(in, fan_topic(in, s), a, b);
+        fan_row(in, fan_topic_of(in, lo, s), a, b);
         const uint64_t at = a + j < in.nmember ? a + j : in.nmember - 1;   // a + j < b <= nmember
         const uint32_t d = in.member[at];
         k = d == me && !in.self ? 2u * in.ndest : 2u * d;
@@ -318,7 +368,11 @@ hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* self
     fan3* total = ex + in.rep_cap;   // one value; 16 are set aside
     fan3* tmp = ex + in.rep_cap + 16;
     const uint32_t rb = (uint32_t)((in.rep_cap + 255) / 256);
-    if (in.nseg) {
+    if (in.rtopic) {   // per publication: four replies per workgroup
+        if (in.rep_cap) hipLaunchKernelGGL(k_fan_self_reply, dim3((uint32_t)((in.rep_cap + 3) / 4)), dim3(256), 0, st, in, selfc, segbad);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else if (in.nseg) {
         hipError_t e = hipMemsetAsync(mark, 0, (uint64_t)in.nseg * 4, st);
         if (e != hipSuccess) return e;
         if (rb) hipLaunchKernelGGL(k_fan_mark, dim3(rb), dim3(256), 0, st, in, mark);

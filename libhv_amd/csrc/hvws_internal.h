@@ -617,7 +617,9 @@ hipError_t launch_replies(const dmsg* msgs, const uint64_t* mg_meta, uint64_t ca
 // kernels read: the reply table of launch_replies (rep, piece, the count word
 // clamped to rep_cap), the piece table it answers (pieces, mg_meta[2] clamped to
 // piece_cap), dest_of / pub per segment (device; pub may be null), and the
-// caller's subscription table.
+// caller's subscription table.  rtopic (null: hvws_fanout): the topic per
+// REPLY that launch_route left, in place of pub[segment] -- hvws_fanout_routed;
+// rep is then the routed rows.
 struct fan_tables {
     const dtxmsg* rep;
     const uint64_t* piece;
@@ -635,6 +637,7 @@ struct fan_tables {
     uint64_t nmember;
     uint32_t ndest;
     bool self;   // HVWS_FAN_SELF
+    const uint32_t* rtopic = nullptr;
 };
 uint64_t fan_scratch_bytes(uint64_t cap);      // the edge scan over cap replies
 uint32_t fan_sort_passes(uint32_t ndest);      // ceil(bits(2 ndest) / 8)
@@ -645,7 +648,8 @@ uint64_t fan_hist_words(uint64_t nedges);      // histogram, its scan and the sc
 // then meta[0..3] = edges before the self drop, deliveries, bad replies (their
 // topic row leaves the member table, a member id is >= ndest, or their piece is
 // none of the batch), replies.  No read leaves topic_first[0 .. ntopics] or
-// member[0 .. nmember).
+// member[0 .. nmember).  With rtopic the self edges and the row checks are per
+// publication: selfc and segbad hold rep_cap words each, mark is not used.
 hipError_t launch_fan_count(const fan_tables& in, uint32_t* mark, uint64_t* selfc, uint32_t* segbad, void* scratch,
                             uint64_t* meta, hipStream_t st);
 // Expansion, sort and finish for nedges edges of which ndel are delivered (both
@@ -663,6 +667,44 @@ hipError_t launch_fan_deliver(const fan_tables& in, const void* scratch, uint64_
 uint32_t fan_key_passes(uint64_t max_key);     // ceil(bits(max_key) / 8)
 hipError_t launch_fan_sort(uint32_t* const key[2], uint32_t* const val[2], uint64_t n, uint32_t passes, uint64_t* hist,
                            int* cur, hipStream_t st);
+// hvws_route (hvws_route.hip; include/hvws.h has the contract).  What its
+// kernels read: the reply table and the piece table as fan_tables names them,
+// dest_of per segment (device), and at most 12 bytes per TEXT / BINARY reply of
+// the message call's output out[0, out_cap).
+struct dsubev;   // mirrors hvws_sub_event (below)
+enum : uint32_t { RK_OTHER = 0u, RK_PUB = 1u, RK_SUB = 2u, RK_UNSUB = 3u, RK_BAD = 4u, RK_STOPPED = 5u, RT_BAD = 1u };
+struct route_tables {
+    const dtxmsg* rep;
+    const uint64_t* piece;
+    const uint64_t* nrep_dev;
+    uint64_t rep_cap;
+    const dmsg* pieces;
+    const uint64_t* mg_meta;
+    uint64_t piece_cap;
+    uint32_t nseg;
+    const uint32_t* dest_of;
+    uint32_t ntopics;
+    const uint8_t* out;
+    uint64_t out_cap;
+};
+// What they write: rows / topic / kind (rep_cap entries each), bad_reply and
+// flags per segment, the dense event table ev (rep_cap entries), scratch
+// (route_scratch_bytes(rep_cap)), meta (8 words): [0] events, [1..4] =
+// publications, subscribes, unsubscribes, bad + stopped.
+struct route_work {
+    dtxmsg* rows;
+    uint32_t* topic;
+    uint8_t* kind;
+    uint64_t* bad_reply;
+    uint8_t* flags;
+    dsubev* ev;
+    void* scratch;
+    uint64_t* meta;
+};
+uint64_t route_scratch_bytes(uint64_t cap);
+// The whole pass, no wait.  No read leaves [off, off + min(len, 12)) of a reply,
+// nor out[0, out_cap).
+hipError_t launch_route(const route_tables& t, const route_work& w, hipStream_t st);
 // hvws_budget (hvws_budget.hip; include/hvws.h has the contract).  What its
 // kernels read: the delivery table of launch_fan_deliver (rows, reply, n of them
 // -- the host knows the count), its sorted keys, first / count per destination,
