@@ -49,6 +49,11 @@
  *                device -- publish to a topic, subscribe, unsubscribe -- into a
  *                topic per reply for hvws_fanout_routed and the join / leave
  *                events for hvws_subs_update.
+ *   hvws_subs_update_routed  what the event loop does when a channel closes
+ *                (evpp/TcpServer.h removeChannel) together with the turn's own
+ *                subscribe commands: hvws_subs_update over the route's events, a
+ *                drop per closed, failed, malformed or over-limit connection and
+ *                the host's own events, merged on the device in that order.
  *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -1063,7 +1068,8 @@ int hvws_get_dest_fanout(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
  *     or produce an event; PONG and CLOSE replies of s are untouched (they are
  *     the reply call's business).  flags[s] gets HVWS_RT_BAD and bad_reply[s] =
  *     b[s], HVWS_ROUTE_NONE without one.  The host closes the connection (with
- *     1008, or what it likes) and passes it to hvws_subs_update as a DROP.  In
+ *     1008, or what it likes) and passes it to hvws_subs_update as a DROP
+ *     (hvws_subs_update_routed makes that DROP on the device).  In
  *     the RFC form a connection's data replies are in stream order, so b[s] is
  *     its first malformed message in the stream.
  *   - events: a dense table, one hvws_sub_event per SUB (HVWS_SUB_JOIN) and
@@ -1179,7 +1185,8 @@ int hvws_fanout_routed(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint3
  * bytes are byte_off[d] .. byte_off[d + 1], equal to d_msg_off[first[d]] ..
  * d_msg_off[first[d] + count[d]], and out[1] of the totals is that call's
  * exact *out_len: the out_cap to allocate.  The host closes the OVER
- * destinations and passes them to hvws_subs_update as HVWS_SUB_DROP events.
+ * destinations and passes them to hvws_subs_update as HVWS_SUB_DROP events
+ * (hvws_subs_update_routed with HVWS_SUBS_OVER makes them on the device).
  *
  * Asynchronous on the ctx stream, no wait; hvws_last_kernel_ms reports it when
  * it was the last call.  It writes nothing the fan-out's getters, the reply
@@ -1281,6 +1288,64 @@ int hvws_subs_update(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_
                      uint64_t member_cap, uint64_t* out_nmember);
 int64_t hvws_subs_count(hvws_ctx* ctx);
 int hvws_get_subs_counts(hvws_ctx* ctx, uint64_t out[4]);
+
+/* hvws_subs_update_routed is hvws_subs_update for a turn that ran hvws_route:
+ * the turn's joins, leaves and drops are on the device already -- the route's
+ * event table, the reply call's and the route's per-segment flags, the
+ * budget's per-destination flags -- and this call merges them there with the
+ * host's own events instead of the host reading all of them, building the DROPs
+ * and sending the lot back up.  ntopics, ndest and dest_of are those of the
+ * valid hvws_route on ctx, as for hvws_fanout_routed.
+ *
+ * The merged event array M is, in this order:
+ *   1. the route's events, in its table order;
+ *   2. one {HVWS_SUB_DROP, 0, dest_of[s]} for every segment s of the reply call
+ *      whose reply flags hold HVWS_RF_CLOSED (a failed connection carries it) or
+ *      whose route flags hold HVWS_RT_BAD -- in segment order, one per segment,
+ *      duplicates not merged;
+ *   3. with HVWS_SUBS_OVER, one {HVWS_SUB_DROP, 0, d} for every destination d
+ *      whose flags in the valid hvws_budget on ctx hold HVWS_BF_OVER, d ascending;
+ *   4. the caller's events[0 .. nev) in array order: the service's own decisions,
+ *      and the JOIN of a new connection that took a closed id over.  They stand
+ *      because they come last.
+ * The result -- both output arrays, *out_nmember, hvws_subs_count and
+ * hvws_get_subs_counts -- is exactly that of hvws_subs_update(ctx,
+ * d_topic_first, d_member, ntopics, nmember, ndest, M, |M|, NULL,
+ * flags & HVWS_SUBS_UNIQUE, ...).  The fourth count is therefore 0: there is no
+ * step-2 drop, the closed connections are events.  A DROP kills every listing
+ * with a stamp at or below its own, so (2) removes the old listings as step 2
+ * would -- and the listings the same turn's route events added: a connection
+ * that sends "S7\n" and a CLOSE in one read ends up listed nowhere, which the
+ * step-2 drop of hvws_subs_update fed the route's events does not give (it
+ * applies before every event).
+ *
+ * Waits twice: once for the merged count (40 bytes) behind the merge kernels --
+ * the sort and rank areas are sized by it -- and once as hvws_subs_update does.
+ * Everything else is asynchronous on the ctx stream; hvws_last_kernel_ms reports
+ * the placement.  No event crosses to the host except the caller's own.
+ * HVWS_EINVAL, with neither output array written and hvws_subs_count reporting
+ * none: no valid hvws_route on ctx (a later route, reply, message call or scan
+ * ends it); HVWS_SUBS_OVER without a valid hvws_budget on ctx, or with one whose
+ * ndest is not the route's; a flag bit outside HVWS_SUBS_UNIQUE |
+ * HVWS_SUBS_OVER; a host event with op outside 1 .. 3, a JOIN / LEAVE topic >=
+ * ntopics or a dest >= ndest (checked before anything is launched); nmember or
+ * |M| above 2^32 - 2; and everything hvws_subs_update refuses about the tables
+ * (NULLs, overlap, alignment, a table that is not dense, a member id >= ndest, a
+ * new nmember above member_cap with *out_nmember still set).  No read leaves
+ * the route's, the reply call's or the budget's tables or the caller's table,
+ * and the call invalidates none of them: it may run anywhere behind hvws_route,
+ * with HVWS_SUBS_OVER behind hvws_budget.  hvws_get_subs_merged: the counts of
+ * the four parts of M; hvws_get_subs_events: M[first .. first + n) (waits; a
+ * range beyond |M| is HVWS_EINVAL).  Both are HVWS_EINVAL before any
+ * hvws_subs_update_routed and after a plain hvws_subs_update.  M is a function
+ * of the input: no atomic places an event.   */
+#define HVWS_SUBS_OVER 2u   /* hvws_subs_update_routed only: drop the last hvws_budget's OVER destinations */
+int hvws_subs_update_routed(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                            const hvws_sub_event* events, uint64_t nev, uint32_t flags,
+                            uint64_t* d_topic_first_out, uint32_t* d_member_out, uint64_t member_cap,
+                            uint64_t* out_nmember);
+int hvws_get_subs_merged(hvws_ctx* ctx, uint64_t out[4]);   /* route events, connection drops, OVER drops, host events */
+int hvws_get_subs_events(hvws_ctx* ctx, hvws_sub_event* out, uint64_t first, uint64_t n);  /* the merged array; waits */
 
 /* Batches of at most `bytes` (default 64 MiB; each segment <= 1 MiB) take
  * the single-launch small-batch path inside hvws_rx_batch (and so inside

@@ -101,6 +101,7 @@ BF_OVER = 1
 # HVWS_SUB_*, HVWS_SUBS_UNIQUE and hvws_sub_event (hvws_subs_update)
 SUB_JOIN, SUB_LEAVE, SUB_DROP = 1, 2, 3
 SUBS_UNIQUE = 1
+SUBS_OVER = 2   # hvws_subs_update_routed only
 SUB_EVENT_DTYPE = np.dtype([("op", "<u4"), ("topic", "<u4"), ("dest", "<u4")])
 assert SUB_EVENT_DTYPE.itemsize == 12
 # HVWS_ROUTE_*, HVWS_RK_* and HVWS_RT_BAD (hvws_route)
@@ -288,6 +289,13 @@ _SIGS = {
     ),
     "hvws_subs_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "hvws_get_subs_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_subs_update_routed": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "hvws_get_subs_merged": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_get_subs_events": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
     "hvws_wsp_new": (ctypes.c_void_p, []),
     "hvws_wsp_free": (None, [ctypes.c_void_p]),
     "hvws_wsp_set_sink": (None, [ctypes.c_void_p, MSG_CB, ctypes.c_void_p]),
@@ -983,6 +991,42 @@ class Engine:
         out = (ctypes.c_uint64 * 4)()
         _check(lib().hvws_get_subs_counts(self.ctx, out), "hvws_get_subs_counts")
         return tuple(int(x) for x in out)
+
+    def subs_update_routed(self, topic_first, member, nmember: int, events, topic_first_out, member_out,
+                           member_cap: int, flags: int = 0) -> int:
+        """hvws_subs_update_routed: subs_update() with the events merged on the
+        device -- the last route() call's events, a DROP per connection the reply
+        call closed or the route found malformed, with SUBS_OVER a DROP per
+        destination the last budget() cut, then `events` (the host's own; may be
+        empty).  ntopics, ndest and dest_of are the route call's.  Returns the new
+        nmember; last_subs_nmember holds it even when the call fails for
+        member_cap."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        if isinstance(events, np.ndarray) and events.dtype == SUB_EVENT_DTYPE:
+            ev = np.ascontiguousarray(events)
+        else:
+            ev = np.array([tuple(e) for e in events], dtype=SUB_EVENT_DTYPE)
+        n = ctypes.c_uint64(0)
+        rc = lib().hvws_subs_update_routed(self.ctx, dev(topic_first), dev(member), nmember,
+                                           ev.ctypes.data if ev.size else None, ev.size, flags, dev(topic_first_out),
+                                           dev(member_out), member_cap, ctypes.byref(n))
+        self.last_subs_nmember = int(n.value)
+        _check(rc, "hvws_subs_update_routed")
+        return int(n.value)
+
+    def subs_merged(self) -> Tuple[int, int, int, int]:
+        """(route events, connection drops, OVER drops, host events) of the last
+        subs_update_routed() call: the four parts of its merged event array."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hvws_get_subs_merged(self.ctx, out), "hvws_get_subs_merged")
+        return tuple(int(x) for x in out)
+
+    def subs_events(self) -> np.ndarray:
+        """The merged event array [SUB_EVENT_DTYPE] of the last subs_update_routed() call."""
+        n = sum(self.subs_merged())
+        out = np.zeros(n, dtype=SUB_EVENT_DTYPE)
+        _check(lib().hvws_get_subs_events(self.ctx, out.ctypes.data, 0, n), "hvws_get_subs_events")
+        return out
 
     def digest(self, buf: DeviceBuffer, n: int) -> int:
         out = ctypes.c_uint64(0)

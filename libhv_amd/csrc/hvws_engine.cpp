@@ -332,14 +332,21 @@ struct pass_budget {
 // listing, the ranks over the
 // events and over the listings, {new nmember, kept, added, removed, dropped,
 // bad} with the two counters behind them.  h: those counts on the host.
+// hvws_subs_update_routed: the merged event array, the two compactions' ranks
+// and scratch, {route events, connection drops, OVER drops, host events, their
+// sum}.  merged: the last call was that one and its merge was read (m: those
+// counts on the host).
 struct pass_subs {
     dbuf in, drop, ping, pong, hist, pk, evfirst, bits, surv, brow, erank, lrank, meta;
+    dbuf mev, mscan, mcnt;
     up_slot up;
     bool have = false;
+    bool merged = false;
     uint64_t h[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t m[5] = {0, 0, 0, 0, 0};
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&in, &drop, &ping, &pong, &hist, &pk, &evfirst, &bits, &surv, &brow, &erank, &lrank,
-                                        &meta});
+                                        &meta, &mev, &mscan, &mcnt});
         up.release(ph);
     }
 };
@@ -4244,10 +4251,92 @@ static_assert(HVWS_SUB_JOIN == 1u && HVWS_SUB_LEAVE == 2u && HVWS_SUB_DROP == 3u
                   RF_CLOSED == HVWS_RF_CLOSED,
               "subscription update constants");
 
+static_assert(HVWS_SUBS_OVER == 2u, "subscription update flag bits");
+
 namespace {
 bool ranges_meet(const void* a, uint64_t na, const void* b, uint64_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+// What hvws_subs_update and hvws_subs_update_routed refuse about the caller's
+// arrays before anything is launched.
+int subs_check_tables(const char* who, const uint64_t* d_topic_first, const uint32_t* d_member, uint32_t ntopics,
+                      uint64_t nmember, const hvws_sub_event* events, uint64_t nev, uint64_t* d_topic_first_out,
+                      uint32_t* d_member_out, uint64_t member_cap) {
+    if (!d_topic_first || !d_topic_first_out || (!d_member && nmember) || (!d_member_out && member_cap) ||
+        (!events && nev))
+        return set_err(HVWS_EINVAL, "%s: null table", who);
+    if (((uintptr_t)d_topic_first_out & 15u) || ((uintptr_t)d_member_out & 15u))
+        return set_err(HVWS_EINVAL, "%s: the output arrays must be 16-byte aligned", who);
+    const uint64_t fb = ((uint64_t)ntopics + 1) * 8, mb = std::min<uint64_t>(member_cap, 1ull << 32) * 4;
+    if (ranges_meet(d_topic_first_out, fb, d_topic_first, fb) || ranges_meet(d_topic_first_out, fb, d_member, nmember * 4) ||
+        ranges_meet(d_member_out, mb, d_topic_first, fb) || ranges_meet(d_member_out, mb, d_member, nmember * 4) ||
+        ranges_meet(d_member_out, mb, d_topic_first_out, fb))
+        return set_err(HVWS_EINVAL, "%s: an output array overlaps another array of the call", who);
+    return HVWS_OK;
+}
+
+// ... and about the host's events.
+int subs_check_events(const char* who, const hvws_sub_event* events, uint64_t nev, uint32_t ntopics, uint32_t ndest) {
+    for (uint64_t e = 0; e < nev; ++e) {
+        const hvws_sub_event& v = events[e];
+        if (v.op < HVWS_SUB_JOIN || v.op > HVWS_SUB_DROP)
+            return set_err(HVWS_EINVAL, "%s: events[%llu].op = %u", who, (unsigned long long)e, v.op);
+        if (v.op != HVWS_SUB_DROP && v.topic >= ntopics)
+            return set_err(HVWS_EINVAL, "%s: events[%llu].topic = %u of %u topics", who, (unsigned long long)e, v.topic,
+                           ntopics);
+        if (v.dest >= ndest)
+            return set_err(HVWS_EINVAL, "%s: events[%llu].dest = %u of %u destinations", who, (unsigned long long)e,
+                           v.dest, ndest);
+    }
+    return HVWS_OK;
+}
+
+// What the two calls share once their events stand in device memory (t.ev,
+// t.nev of them): the work areas, the counting kernels, the one wait, the
+// placement.
+int subs_run(hvws_ctx* c, const char* who, const subs_tables& t, uint64_t* d_topic_first_out, uint32_t* d_member_out,
+             uint64_t member_cap, uint64_t* out_nmember) {
+    int rc;
+    pass_subs& p = c->subs;
+    const uint64_t nev = t.nev, nmember = t.nmember;
+    HIP_OR(p.drop.ensure((uint64_t)t.ndest * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.ping.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.pong.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.hist.ensure(fan_hist_words(nev) * 8), HVWS_ENOMEM);
+    HIP_OR(p.pk.ensure(nev * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.evfirst.ensure(((uint64_t)t.ntopics + 1) * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.bits.ensure(nev * 3 + 16), HVWS_ENOMEM);
+    HIP_OR(p.surv.ensure(nmember + 16), HVWS_ENOMEM);
+    HIP_OR(p.brow.ensure((nmember / 256 + 2) * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.erank.ensure(subs_event_rank_words(nev) * 8), HVWS_ENOMEM);
+    HIP_OR(p.lrank.ensure(subs_rank_words(nmember) * 8), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(128), HVWS_ENOMEM);
+    uint32_t* key0 = p.ping.as<uint32_t>();
+    uint32_t* key1 = p.pong.as<uint32_t>();
+    uint8_t* bits = p.bits.as<uint8_t>();
+    const subs_work w{p.drop.as<uint32_t>(), {key0, key1}, {key0 + nev, key1 + nev}, p.hist.as<uint64_t>(),
+                      p.pk.as<uint64_t>(), p.evfirst.as<uint64_t>(), bits, bits + nev, bits + 2 * nev, p.surv.as<uint8_t>(), p.brow.as<uint32_t>(),
+                      p.erank.as<uint64_t>(), p.lrank.as<uint64_t>(), p.meta.as<uint64_t>()};
+    HIP_OR(launch_subs_count(t, w, c->stream), HVWS_EHIP);
+    // the one wait: new nmember, kept, added, removed, destinations dropped as closed, bad
+    uint64_t h[6] = {0, 0, 0, 0, 0, 0};
+    if ((rc = read_rows(c, {{h, w.meta, sizeof h}})) != HVWS_OK) return rc;
+    if (h[5])
+        return set_err(HVWS_EINVAL, "%s: the table is not dense (topic_first[0] != 0, a decreasing pair, "
+                       "topic_first[ntopics] != nmember) or holds a member id outside the destinations", who);
+    if (out_nmember) *out_nmember = h[0];
+    if (h[0] > member_cap)
+        return set_err(HVWS_EINVAL, "%s: %llu listings, member_cap %llu", who, (unsigned long long)h[0],
+                       (unsigned long long)member_cap);
+    // the timed device work (hvws_last_kernel_ms): the placement
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_subs_place(t, w, h[0], d_topic_first_out, d_member_out, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    memcpy(p.h, h, sizeof h);
+    return HVWS_OK;
 }
 }  // namespace
 
@@ -4262,33 +4351,17 @@ int hvws_subs_update(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t*
     if (rc) return rc;
     if (out_nmember) *out_nmember = 0;
     c->subs.have = false;
+    c->subs.merged = false;
     if (flags & ~(uint32_t)HVWS_SUBS_UNIQUE) return set_err(HVWS_EINVAL, "hvws_subs_update: unknown flag bits");
     if (ndest == 0 || ndest > 0x7FFFFFFFu)
         return set_err(HVWS_EINVAL, "hvws_subs_update: %u destinations (1 .. 2^31-1)", ndest);
     if (nmember > 0xFFFFFFFEull || nev > 0xFFFFFFFEull)
         return set_err(HVWS_EINVAL, "hvws_subs_update: %llu listings, %llu events (max 2^32-2 each)",
                        (unsigned long long)nmember, (unsigned long long)nev);
-    if (!d_topic_first || !d_topic_first_out || (!d_member && nmember) || (!d_member_out && member_cap) ||
-        (!events && nev))
-        return set_err(HVWS_EINVAL, "hvws_subs_update: null table");
-    if (((uintptr_t)d_topic_first_out & 15u) || ((uintptr_t)d_member_out & 15u))
-        return set_err(HVWS_EINVAL, "hvws_subs_update: the output arrays must be 16-byte aligned");
-    const uint64_t fb = ((uint64_t)ntopics + 1) * 8, mb = std::min<uint64_t>(member_cap, 1ull << 32) * 4;
-    if (ranges_meet(d_topic_first_out, fb, d_topic_first, fb) || ranges_meet(d_topic_first_out, fb, d_member, nmember * 4) ||
-        ranges_meet(d_member_out, mb, d_topic_first, fb) || ranges_meet(d_member_out, mb, d_member, nmember * 4) ||
-        ranges_meet(d_member_out, mb, d_topic_first_out, fb))
-        return set_err(HVWS_EINVAL, "hvws_subs_update: an output array overlaps another array of the call");
-    for (uint64_t e = 0; e < nev; ++e) {
-        const hvws_sub_event& v = events[e];
-        if (v.op < HVWS_SUB_JOIN || v.op > HVWS_SUB_DROP)
-            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].op = %u", (unsigned long long)e, v.op);
-        if (v.op != HVWS_SUB_DROP && v.topic >= ntopics)
-            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].topic = %u of %u topics", (unsigned long long)e,
-                           v.topic, ntopics);
-        if (v.dest >= ndest)
-            return set_err(HVWS_EINVAL, "hvws_subs_update: events[%llu].dest = %u of %u destinations",
-                           (unsigned long long)e, v.dest, ndest);
-    }
+    if ((rc = subs_check_tables("hvws_subs_update", d_topic_first, d_member, ntopics, nmember, events, nev,
+                                d_topic_first_out, d_member_out, member_cap)) != HVWS_OK)
+        return rc;
+    if ((rc = subs_check_events("hvws_subs_update", events, nev, ntopics, ndest)) != HVWS_OK) return rc;
     uint32_t nseg = 0;
     if (dest_of) {
         if (!c->rp.have) return set_err(HVWS_EINVAL, "hvws_subs_update: dest_of without a preceding hvws_replies");
@@ -4301,18 +4374,6 @@ int hvws_subs_update(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t*
     }
     pass_subs& p = c->subs;
     HIP_OR(p.in.ensure(nev * 12 + (uint64_t)nseg * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(p.drop.ensure((uint64_t)ndest * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(p.ping.ensure(nev * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(p.pong.ensure(nev * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(p.hist.ensure(fan_hist_words(nev) * 8), HVWS_ENOMEM);
-    HIP_OR(p.pk.ensure(nev * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(p.evfirst.ensure(((uint64_t)ntopics + 1) * 8 + 16), HVWS_ENOMEM);
-    HIP_OR(p.bits.ensure(nev * 3 + 16), HVWS_ENOMEM);
-    HIP_OR(p.surv.ensure(nmember + 16), HVWS_ENOMEM);
-    HIP_OR(p.brow.ensure((nmember / 256 + 2) * 4 + 16), HVWS_ENOMEM);
-    HIP_OR(p.erank.ensure(subs_event_rank_words(nev) * 8), HVWS_ENOMEM);
-    HIP_OR(p.lrank.ensure(subs_rank_words(nmember) * 8), HVWS_ENOMEM);
-    HIP_OR(p.meta.ensure(128), HVWS_ENOMEM);
     // the events, then dest_of behind them
     const bool drops = dest_of && nseg;
     if (nev)
@@ -4324,30 +4385,75 @@ int hvws_subs_update(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t*
                         drops ? reinterpret_cast<const uint32_t*>(p.in.as<uint8_t>() + nev * 12) : nullptr,
                         drops ? c->rp.flags.as<uint8_t>() : nullptr, drops ? nseg : 0u,
                         (flags & HVWS_SUBS_UNIQUE) != 0};
-    uint32_t* key0 = p.ping.as<uint32_t>();
-    uint32_t* key1 = p.pong.as<uint32_t>();
-    uint8_t* bits = p.bits.as<uint8_t>();
-    const subs_work w{p.drop.as<uint32_t>(), {key0, key1}, {key0 + nev, key1 + nev}, p.hist.as<uint64_t>(),
-                      p.pk.as<uint64_t>(), p.evfirst.as<uint64_t>(), bits, bits + nev, bits + 2 * nev, p.surv.as<uint8_t>(), p.brow.as<uint32_t>(),
-                      p.erank.as<uint64_t>(), p.lrank.as<uint64_t>(), p.meta.as<uint64_t>()};
-    HIP_OR(launch_subs_count(t, w, c->stream), HVWS_EHIP);
-    // the one wait: new nmember, kept, added, removed, destinations dropped as closed, bad
-    uint64_t h[6] = {0, 0, 0, 0, 0, 0};
-    if ((rc = read_rows(c, {{h, w.meta, sizeof h}})) != HVWS_OK) return rc;
-    if (h[5])
-        return set_err(HVWS_EINVAL, "hvws_subs_update: the table is not dense (topic_first[0] != 0, a decreasing pair, "
-                       "topic_first[ntopics] != nmember) or holds a member id outside the destinations");
-    if (out_nmember) *out_nmember = h[0];
-    if (h[0] > member_cap)
-        return set_err(HVWS_EINVAL, "hvws_subs_update: %llu listings, member_cap %llu", (unsigned long long)h[0],
-                       (unsigned long long)member_cap);
-    // the timed device work (hvws_last_kernel_ms): the placement
-    HIP_OR(timed_begin(c), HVWS_EHIP);
-    HIP_OR(launch_subs_place(t, w, h[0], d_topic_first_out, d_member_out, c->stream), HVWS_EHIP);
-    HIP_OR(timed_end(c), HVWS_EHIP);
-    p.have = true;
-    memcpy(p.h, h, sizeof h);
+    return subs_run(c, "hvws_subs_update", t, d_topic_first_out, d_member_out, member_cap, out_nmember);
+}
+
+// hvws_subs_update over the turn's own events, merged on the device
+// (hvws_subs.hip): the route's events, a DROP per closed or malformed
+// connection, with HVWS_SUBS_OVER a DROP per destination the budget cut, then
+// the host's events.  One wait for the merged count, then subs_run.
+int hvws_subs_update_routed(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                            const hvws_sub_event* events, uint64_t nev, uint32_t flags, uint64_t* d_topic_first_out,
+                            uint32_t* d_member_out, uint64_t member_cap, uint64_t* out_nmember) {
+    const char* who = "hvws_subs_update_routed";
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_nmember) *out_nmember = 0;
+    pass_subs& p = c->subs;
+    p.have = false;
+    p.merged = false;
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "%s without a preceding hvws_route", who);
+    if (flags & ~(uint32_t)(HVWS_SUBS_UNIQUE | HVWS_SUBS_OVER)) return set_err(HVWS_EINVAL, "%s: unknown flag bits", who);
+    const bool over = (flags & HVWS_SUBS_OVER) != 0;
+    const uint32_t ntopics = c->rt.ntopics, ndest = c->rt.ndest, nseg = c->rt.nseg;
+    if (over && !budget_valid(c)) return set_err(HVWS_EINVAL, "%s: HVWS_SUBS_OVER without a preceding hvws_budget", who);
+    if (over && c->bg.ndest != ndest)
+        return set_err(HVWS_EINVAL, "%s: hvws_budget ran over %u destinations, hvws_route over %u", who, c->bg.ndest, ndest);
+    if (nmember > 0xFFFFFFFEull || nev > 0xFFFFFFFEull)
+        return set_err(HVWS_EINVAL, "%s: %llu listings, %llu events (max 2^32-2 each)", who, (unsigned long long)nmember,
+                       (unsigned long long)nev);
+    if ((rc = subs_check_tables(who, d_topic_first, d_member, ntopics, nmember, events, nev, d_topic_first_out,
+                                d_member_out, member_cap)) != HVWS_OK)
+        return rc;
+    if ((rc = subs_check_events(who, events, nev, ntopics, ndest)) != HVWS_OK) return rc;
+    const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
+    const uint32_t nover = over ? ndest : 0u;
+    HIP_OR(p.in.ensure(nev * 12 + 16), HVWS_ENOMEM);
+    HIP_OR(p.mev.ensure((cap + nseg + nover + nev + 1) * sizeof(dsubev)), HVWS_ENOMEM);
+    HIP_OR(p.mscan.ensure(subs_merge_words(nseg, nover) * 8), HVWS_ENOMEM);
+    HIP_OR(p.mcnt.ensure(64), HVWS_ENOMEM);
+    if ((rc = p.up.send(p.in.p, c->stream, events, nev * 12)) != HVWS_OK) return rc;
+    const subs_merge mt{c->rt.ev.as<dsubev>(), c->rt.meta.as<uint64_t>(), cap, c->rp.flags.as<uint8_t>(),
+                        c->rt.flags.as<uint8_t>(), c->rt.in.as<uint32_t>(), nseg,
+                        over ? c->bg.flags.as<uint8_t>() : nullptr, nover, p.in.as<dsubev>(), nev};
+    HIP_OR(launch_subs_merge(mt, p.mscan.as<uint64_t>(), p.mev.as<dsubev>(), p.mcnt.as<uint64_t>(), c->stream), HVWS_EHIP);
+    // the first wait: route events, connection drops, OVER drops, host events, their sum
+    uint64_t m[5] = {0, 0, 0, 0, 0};
+    if ((rc = read_rows(c, {{m, p.mcnt.p, sizeof m}})) != HVWS_OK) return rc;
+    if (m[4] > 0xFFFFFFFEull)
+        return set_err(HVWS_EINVAL, "%s: %llu merged events (max 2^32-2)", who, (unsigned long long)m[4]);
+    p.merged = true;
+    memcpy(p.m, m, sizeof m);
+    const subs_tables t{d_topic_first, d_member, ntopics, nmember, ndest, p.mev.as<dsubev>(), m[4], nullptr, nullptr, 0u,
+                        (flags & HVWS_SUBS_UNIQUE) != 0};
+    return subs_run(c, who, t, d_topic_first_out, d_member_out, member_cap, out_nmember);
+}
+
+int hvws_get_subs_merged(hvws_ctx* c, uint64_t out[4]) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->subs.merged) return set_err(HVWS_EINVAL, "no hvws_subs_update_routed call yet");
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_subs_merged: null out");
+    for (int k = 0; k < 4; ++k) out[k] = c->subs.m[k];
     return HVWS_OK;
+}
+
+int hvws_get_subs_events(hvws_ctx* c, hvws_sub_event* out, uint64_t first, uint64_t n) {
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->subs.merged) return set_err(HVWS_EINVAL, "no hvws_subs_update_routed call yet");
+    const uint64_t have = c->subs.m[4];
+    if (first > have || n > have - first) return set_err(HVWS_EINVAL, "merged event range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{out, c->subs.mev.as<dsubev>() + first, n * sizeof(dsubev)}});
 }
 
 int64_t hvws_subs_count(hvws_ctx* c) {

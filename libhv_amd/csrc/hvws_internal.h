@@ -799,6 +799,30 @@ hipError_t launch_subs_count(const subs_tables& t, const subs_work& w, hipStream
 // (ntopics + 1 words) and member_out[0 .. newn).
 hipError_t launch_subs_place(const subs_tables& t, const subs_work& w, uint64_t newn, uint64_t* first_out,
                              uint32_t* member_out, hipStream_t st);
+// The merge of hvws_subs_update_routed.  What its kernels read: the route
+// pass's event table (rt_ev, its count word clamped to rt_cap), per segment the
+// reply call's flags, the route pass's flags and its device copy of dest_of,
+// the budget pass's flags per destination (nover of them; 0: none are read)
+// and the uploaded host events.
+struct subs_merge {
+    const dsubev* rt_ev;
+    const uint64_t* rt_nev;
+    uint64_t rt_cap;
+    const uint8_t* rflags;
+    const uint8_t* rtflags;
+    const uint32_t* dest_of;
+    uint32_t nseg;
+    const uint8_t* bflags;
+    uint32_t nover;
+    const dsubev* host_ev;
+    uint64_t nev;
+};
+uint64_t subs_merge_words(uint32_t nseg, uint32_t nover);
+// Two scans (scratch: subs_merge_words words) and the append, no wait: out
+// (rt_cap + nseg + nover + nev entries) = the route's events, a DROP per closed
+// or malformed segment, a DROP per OVER destination, the host's events;
+// meta[0..4] = those four counts and their sum.
+hipError_t launch_subs_merge(const subs_merge& t, uint64_t* scratch, dsubev* out, uint64_t* meta, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125

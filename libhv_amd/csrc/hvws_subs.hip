@@ -43,6 +43,13 @@
 // topic's few events), 4 B of drop[], 1 B written, 8 B of
 // rank written and read, 4 B written.  Per event: 12 B up, 8 B + 8 B per sort pass (hvws_fan.hip), 9 B of
 // pair and kind, 16 B of ranks.
+//
+// hvws_subs_update_routed puts a merge in front of all that (launch_subs_merge):
+// the event array is built on the device from the route pass's events, a DROP
+// per closed or malformed segment, a DROP per OVER destination and the host's
+// own events -- two compactions by the scan of hvws_dev.h and one append
+// kernel; 12 B read and written per event, 2 B of flags and 8 B of rank per
+// segment, 1 B and 8 B per destination.
 #include "hvws_dev.h"
 
 namespace hvws {
@@ -290,7 +297,74 @@ __global__ __launch_bounds__(256) void k_subs_place_join(subs_in in, const uint6
 
 inline dim3 grid_of(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
+// ---- the merge of hvws_subs_update_routed: four dense appends ----
+// Segment s gives a DROP iff the reply call closed it or the route call found it
+// malformed; destination d iff the budget call cut it.  Both are inlined into a
+// scan functor and into k_subs_merge: values by selects, no early return
+// (hvws_route.hip, route_kind, has the miscompile that shape met).
+__device__ __forceinline__ uint64_t merge_seg_drop(const subs_merge& in, uint64_t s) {
+    return ((in.rflags[s] & RF_CLOSED) | (in.rtflags[s] & RT_BAD)) != 0 ? 1u : 0u;
+}
+__device__ __forceinline__ uint64_t merge_over(const subs_merge& in, uint64_t d) {
+    return (in.bflags[d] & BF_OVER) != 0 ? 1u : 0u;
+}
+struct merge_seg_load {
+    subs_merge in;
+    __device__ __forceinline__ uint64_t operator()(uint64_t s) const { return merge_seg_drop(in, s); }
+};
+struct merge_over_load {
+    subs_merge in;
+    __device__ __forceinline__ uint64_t operator()(uint64_t d) const { return merge_over(in, d); }
+};
+
+// One thread per route event, segment, destination and host event (the grid
+// covers the largest of the four capacities): out = the route's events, the
+// connection drops in segment order, the OVER drops in destination order, the
+// host's events; meta[0..4] = the four counts and their sum.  srank / orank: the
+// exclusive scans of the two predicates, nsd / nod their totals.
+__global__ __launch_bounds__(256) void k_subs_merge(subs_merge in, const uint64_t* __restrict__ srank,
+                                                    const uint64_t* __restrict__ nsd,
+                                                    const uint64_t* __restrict__ orank,
+                                                    const uint64_t* __restrict__ nod, dsubev* __restrict__ out,
+                                                    uint64_t* __restrict__ meta) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t have = *in.rt_nev;
+    const uint64_t nrt = have < in.rt_cap ? have : in.rt_cap;
+    const uint64_t b1 = nrt, b2 = b1 + *nsd, b3 = b2 + *nod;
+    if (i == 0) {
+        meta[0] = nrt;
+        meta[1] = *nsd;
+        meta[2] = *nod;
+        meta[3] = in.nev;
+        meta[4] = b3 + in.nev;
+    }
+    if (i < nrt) out[i] = in.rt_ev[i];
+    if (i < in.nseg && merge_seg_drop(in, i)) out[b1 + srank[i]] = dsubev{OP_DROP, 0u, in.dest_of[i]};
+    if (i < in.nover && merge_over(in, i)) out[b2 + orank[i]] = dsubev{OP_DROP, 0u, (uint32_t)i};
+    if (i < in.nev) out[b3 + i] = in.host_ev[i];
+}
+
 }  // namespace
+
+uint64_t subs_merge_words(uint32_t nseg, uint32_t nover) {
+    return (uint64_t)nseg + nover + 32 + scan_tmp_words(nseg > nover ? nseg : nover);
+}
+
+hipError_t launch_subs_merge(const subs_merge& t, uint64_t* scratch, dsubev* out, uint64_t* meta, hipStream_t st) {
+    uint64_t* srank = scratch;
+    uint64_t* nsd = srank + t.nseg;                   // one value each; 16 are set aside
+    uint64_t* orank = nsd + 16;
+    uint64_t* nod = orank + t.nover;
+    uint64_t* tmp = nod + 16;
+    hipError_t e = launch_scan_of(merge_seg_load{t}, srank, t.nseg, tmp, nsd, st);
+    if (e != hipSuccess) return e;
+    e = launch_scan_of(merge_over_load{t}, orank, t.nover, tmp, nod, st);
+    if (e != hipSuccess) return e;
+    const uint64_t n = std::max<uint64_t>(std::max<uint64_t>(t.rt_cap, t.nev), std::max<uint32_t>(t.nseg, t.nover));
+    hipLaunchKernelGGL(k_subs_merge, grid_of(std::max<uint64_t>(n, 1)), dim3(256), 0, st, t, srank, nsd, orank, nod, out,
+                       meta);
+    return hipGetLastError();
+}
 
 uint64_t subs_rank_words(uint64_t n) { return n + 16 + scan_tmp_words(n); }
 uint64_t subs_event_rank_words(uint64_t nev) { return 2 * nev + 16 + scan_tmp_words(nev); }
