@@ -54,6 +54,10 @@
  *                subscribe commands: hvws_subs_update over the route's events, a
  *                drop per closed, failed, malformed or over-limit connection and
  *                the host's own events, merged on the device in that order.
+ *   hvws_retain  a last-value cache (user code in the reference; MQTT's retained
+ *                message): each topic's last publication kept in a
+ *                device-resident store, and a snapshot row per subscribe of the
+ *                turn for a second hvws_send_messages.
  *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -1136,6 +1140,106 @@ int hvws_get_route_flags(hvws_ctx* ctx, uint8_t* flags, uint64_t* bad_reply);
 int hvws_get_route_totals(hvws_ctx* ctx, uint64_t out[4]);
 int hvws_fanout_routed(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
                        uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries);
+
+/* ---- each topic's last message for joiners, device resident ----------------- */
+/* A connection that subscribes to a topic hears nothing until someone publishes
+ * there again; a feed or a room with state wants the last value at once (MQTT's
+ * retained message, a last-value cache).  hvws_retain keeps each topic's most
+ * recent publication in a store in device memory and leaves, for the turn's
+ * subscribes, the rows a second hvws_send_messages sends from that store -- no
+ * message byte, publication or subscribe command goes to the host.  The
+ * reference has no counterpart: its onmessage is user code.
+ *
+ * The store is the caller's, in device memory, kept across turns and updated in
+ * place: d_store holds ntopics slots of `slot` bytes, topic t's slot being
+ * [t * slot, (t + 1) * slot), and d_ret holds ntopics entries.  ntopics, ndest
+ * and dest_of are those of the valid hvws_route on ctx, as for
+ * hvws_fanout_routed.  An entry counts as retained iff set == 1 and
+ * 0 < len <= slot; anything else is "nothing retained", whatever the caller put
+ * there.  The caller seeds both with hvws_memset to 0, or uploads values of its
+ * own.
+ *
+ * The rule, over the routed replies i = 0 .. nr - 1 in table order:
+ *   1. Update.  Of the replies of final kind HVWS_RK_PUB to topic t, the last
+ *      (the largest i) wins; its trimmed body is [off, off + len) of the message
+ *      call's d_out.
+ *        - 0 < len <= slot: the body is copied to the front of slot t and
+ *          d_ret[t] = {len, the routed row's flags, 1};
+ *        - len == 0: d_ret[t] becomes all zero (an empty publication clears, as
+ *          in MQTT);
+ *        - len > slot: d_ret[t] becomes all zero and the topic is counted as
+ *          oversize (a stale value is worse than none).
+ *      A topic without a publication this turn is untouched: the update neither
+ *      reads nor writes its entry or its slot.  BAD, STOPPED, SUB and UNSUB
+ *      replies and PONG / CLOSE retain nothing.  Whether hvws_budget later cut a
+ *      delivery does not matter: what was published is retained.
+ *   2. Snapshot, taken after the update.  Every reply of final kind HVWS_RK_SUB
+ *      (= every JOIN event of the route) whose topic t is retained produces one
+ *      row {off = t * slot, len = d_ret[t].len, flags = d_ret[t].flags, key = 0}.
+ *      The rows are dense and in reply order; topic[k] and reply[k] name row k's
+ *      topic and SUB reply.  Replies are ordered by segment, so each segment's
+ *      rows are contiguous: first[s] / count[s] (hvws_get_dest_fanout's
+ *      convention for a segment without rows: the next segment's first, count
+ *      0).  A subscription takes effect in the next turn's table, so with the
+ *      snapshot taken after this turn's update a joiner misses nothing and gets
+ *      nothing twice.  The device does not know who is a member already: a
+ *      subscribe by a connection that is one gets a snapshot again.  A subscribe
+ *      by a connection that also closes this turn still has its row; the caller
+ *      does not write that connection's range.
+ *   3. Send.  hvws_send_messages(ctx, d_tx2, cap2, d_store, ntopics * slot,
+ *      hvws_retain_device(ctx), hvws_reply_capacity(ctx),
+ *      hvws_retain_count_device(ctx), fragment, 0, d_msg_off2, ...) builds the
+ *      snapshot frames; segment s's bytes are d_msg_off2[first[s]] ..
+ *      d_msg_off2[first[s] + count[s]].  The caller writes them behind the
+ *      connection's range of the turn's main send, and not at all for a
+ *      connection the turn closed, failed or found malformed.  The snapshot is
+ *      not under hvws_budget: the host holds its range against what byte_off
+ *      left.
+ * The outputs are functions of the input alone: the same on every run, whatever
+ * the kernels' geometry; no atomic places a row or a byte.
+ *
+ * hvws_retain runs behind hvws_route, after any of the three message forms, is
+ * asynchronous on the ctx stream and does not wait; hvws_last_kernel_ms reports
+ * it when it was the last call.  The message call's d_out must still hold that
+ * call's bytes.  It changes nothing the reply, route, fan-out, budget or subs
+ * getters read and invalidates none of them: it may run anywhere behind the
+ * route call.  HVWS_EINVAL, nothing launched and the store untouched: no valid
+ * hvws_route on ctx; a flags bit set (none is defined); slot 0 or not a multiple
+ * of 16, or ntopics * slot beyond 64 bits; with ntopics > 0, d_store or d_ret
+ * NULL or d_store not 16-byte aligned; d_store[0, ntopics * slot), d_ret[0,
+ * ntopics) and the message call's d_out[0, out_cap) overlapping one another.
+ * Reads of a winning body stay inside [off, off + len) rounded outwards to 16
+ * bytes and clipped to [0, out_cap); writes to d_store touch only [t * slot,
+ * t * slot + len) of topics stored this turn; writes to d_ret only entries of
+ * topics with a publication this turn; reads of d_ret only entries of topics
+ * subscribed to and not published to this turn; nothing reads a slot.
+ *
+ * The snapshot tables are valid until the next hvws_retain, hvws_route, reply
+ * call, message call or scan on ctx; every getter reports none after that (the
+ * _device ones NULL, hvws_retain_count -1, the others HVWS_EINVAL).  The store
+ * itself is the caller's and persists.  hvws_retain_device /
+ * hvws_retain_count_device (d_msgs and d_n of hvws_send_messages; its n is
+ * hvws_reply_capacity) do not wait; the others do.  hvws_get_retain: rows
+ * first .. first + n - 1 with the topic and the SUB reply of each, any pointer
+ * may be NULL, a range beyond the row count is HVWS_EINVAL;
+ * hvws_get_segment_retain: nseg entries each, either may be NULL;
+ * hvws_get_retain_totals: topics stored, cleared by an empty publication,
+ * cleared by an oversize one, bytes copied, snapshot rows.  hvws_retain_tile:
+ * the store bytes one workgroup of the copy covers per step (tests place body
+ * lengths around it).   */
+typedef struct hvws_retained {   /* 16 B per topic; all zero = nothing retained */
+    uint64_t len;                /* bytes of the retained body in the topic's slot */
+    uint32_t flags;              /* the routed row's flags (opcode, FIN) */
+    uint32_t set;                /* 1 = a message is retained */
+} hvws_retained;
+int hvws_retain(hvws_ctx* ctx, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags);
+const hvws_tx_msg* hvws_retain_device(hvws_ctx* ctx);
+const uint64_t* hvws_retain_count_device(hvws_ctx* ctx);
+int64_t hvws_retain_count(hvws_ctx* ctx);
+int hvws_get_retain(hvws_ctx* ctx, hvws_tx_msg* rows, uint32_t* topic, uint64_t* reply, uint64_t first, uint64_t n);
+int hvws_get_segment_retain(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
+int hvws_get_retain_totals(hvws_ctx* ctx, uint64_t out[5]);
+uint64_t hvws_retain_tile(void);
 
 /* ---- per-destination write limits for the fan-out, device resident ---------- */
 /* hvws_budget cuts every destination's deliveries of the last hvws_fanout at

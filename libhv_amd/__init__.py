@@ -109,6 +109,9 @@ ROUTE_HDR_MAX = 12
 RK_OTHER, RK_PUB, RK_SUB, RK_UNSUB, RK_BAD, RK_STOPPED = 0, 1, 2, 3, 4, 5
 RT_BAD = 1
 ROUTE_NONE = (1 << 64) - 1
+# hvws_retained (hvws_retain)
+RETAINED_DTYPE = np.dtype([("len", "<u8"), ("flags", "<u4"), ("set", "<u4")])
+assert RETAINED_DTYPE.itemsize == 16
 assert ctypes.sizeof(WsParser) == 48
 
 MSG_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
@@ -268,6 +271,19 @@ _SIGS = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
          ctypes.POINTER(ctypes.c_uint64)],
     ),
+    "hvws_retain": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32]
+    ),
+    "hvws_retain_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_retain_count_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_retain_count": (ctypes.c_int64, [ctypes.c_void_p]),
+    "hvws_get_retain": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64],
+    ),
+    "hvws_get_segment_retain": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "hvws_get_retain_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_retain_tile": (ctypes.c_uint64, []),
     "hvws_budget": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
     ),
@@ -915,6 +931,50 @@ class Engine:
         self.last_deliveries = int(n.value)
         _check(rc, "hvws_fanout_routed")
         return int(n.value)
+
+    def retain(self, store, slot: int, ret, flags: int = 0) -> None:
+        """hvws_retain behind the last route() call: each topic's last publication
+        of the turn into the caller's store (store: ntopics slots of `slot` bytes;
+        ret: ntopics RETAINED_DTYPE entries; DeviceBuffers or device addresses,
+        kept across turns), and a snapshot row per subscribe of the turn whose
+        topic holds a message afterwards.  No wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_retain(self.ctx, dev(store), slot, dev(ret), flags), "hvws_retain")
+
+    def retain_device(self) -> Tuple[int, int, int]:
+        """(table address, count word address, the reply capacity): msgs, d_n and n
+        of the send_messages() that sends the last retain() call's snapshot from
+        the store; (None, None, 0) when there is none."""
+        L = lib()
+        t, d_n = L.hvws_retain_device(self.ctx), L.hvws_retain_count_device(self.ctx)
+        return t, d_n, int(L.hvws_reply_capacity(self.ctx)) if t else 0
+
+    def retain_table(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(snapshot rows [TX_MSG_DTYPE] over the store, the topic, the SUB reply)
+        of the last retain() call, in reply order."""
+        n = lib().hvws_retain_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_retain_count")
+        rows = np.zeros(n, dtype=TX_MSG_DTYPE)
+        topic = np.zeros(n, dtype=np.uint32)
+        reply = np.zeros(n, dtype=np.uint64)
+        _check(lib().hvws_get_retain(self.ctx, rows.ctypes.data, topic.ctypes.data, reply.ctypes.data, 0, n),
+               "hvws_get_retain")
+        return rows, topic, reply
+
+    def segment_retain(self, nseg: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(first snapshot row, row count) per segment of the last retain() call."""
+        first = np.zeros(max(nseg, 1), np.uint64)
+        cnt = np.zeros(max(nseg, 1), np.uint64)
+        _check(lib().hvws_get_segment_retain(self.ctx, first.ctypes.data, cnt.ctypes.data), "hvws_get_segment_retain")
+        return first[:nseg], cnt[:nseg]
+
+    def retain_totals(self) -> Tuple[int, int, int, int, int]:
+        """(topics stored, cleared by an empty publication, cleared by an oversize
+        one, bytes copied, snapshot rows) of the last retain() call."""
+        out = (ctypes.c_uint64 * 5)()
+        _check(lib().hvws_get_retain_totals(self.ctx, out), "hvws_get_retain_totals")
+        return tuple(int(x) for x in out)
 
     def budget(self, budget, budget_all: int = (1 << 64) - 1, fragment: int = 0, masked: bool = False) -> None:
         """hvws_budget over the last fanout() call: every destination's deliveries

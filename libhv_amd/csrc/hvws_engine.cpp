@@ -301,9 +301,27 @@ struct pass_route {
     bool have = false;
     uint32_t nseg = 0, ntopics = 0, ndest = 0;
     uint64_t rep = 0, msg = 0, gen = 0;
+    uint64_t seq = 0;   // route calls so far
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&scan, &in, &rows, &topic, &kind, &bad, &flags, &ev, &meta});
         up.release(ph);
+    }
+};
+
+// hvws_retain: the plan scan's scratch, the winner word per topic, the copy
+// plan (four arrays in one buffer), the snapshot rows with the topic and the
+// SUB reply of each, per-segment first / count, {snapshot rows, stored, cleared
+// empty, cleared oversize, bytes copied, snapshot rows}.  Nothing goes up: no
+// slot.  The store and its entries are the caller's.  route / rep / msg / gen:
+// the route call (pass_route::seq), the reply call, the message call and the
+// scans it ran behind.
+struct pass_retain {
+    dbuf scan, win, plan, rows, topic, reply, first, count, meta;
+    bool have = false;
+    uint32_t nseg = 0;
+    uint64_t route = 0, rep = 0, msg = 0, gen = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &win, &plan, &rows, &topic, &reply, &first, &count, &meta});
     }
 };
 
@@ -476,6 +494,7 @@ struct hvws_ctx {
     pass_replies rp;
     pass_fan fan;
     pass_route rt;
+    pass_retain rn;
     pass_budget bg;
     pass_subs subs;
     pass_check ck;
@@ -2552,6 +2571,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->rp.release(ph);
         c->fan.release(ph);
         c->rt.release(ph);
+        c->rn.release(ph);
         c->bg.release(ph);
         c->subs.release(ph);
         c->ck.release(ph);
@@ -4031,6 +4051,7 @@ int hvws_route(hvws_ctx* c, uint32_t ntopics, uint32_t ndest, const uint32_t* de
     if (rc) return rc;
     pass_route& p = c->rt;
     p.have = false;   // the tables are being rewritten
+    ++p.seq;
     if (!c->rp.have || !c->mg.have) return set_err(HVWS_EINVAL, "hvws_route without a preceding hvws_replies");
     if (c->rp.gen != c->scan_gen) return set_err(HVWS_EINVAL, "hvws_route: a scan has run since hvws_replies");
     if (!dest_of) return set_err(HVWS_EINVAL, "hvws_route: null dest_of");
@@ -4148,6 +4169,118 @@ int hvws_fanout_routed(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_
                        (flags & HVWS_FAN_SELF) != 0, c->rt.topic.as<uint32_t>()};
     return fan_run(c, "hvws_fanout_routed", t, cap, max_deliveries, out_deliveries);
 }
+
+static_assert(sizeof(dretained) == sizeof(hvws_retained) && sizeof(dretained) == 16, "dretained mirrors hvws_retained");
+
+namespace {
+// [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+}  // namespace
+
+// Each topic's last publication of the turn into the caller's store, and the
+// snapshot rows for the turn's subscribes (hvws_retain.hip): the pick, one
+// scan, the finish, the copy.  No wait.
+int hvws_retain(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    pass_retain& p = c->rn;
+    p.have = false;   // the tables are being rewritten
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_retain without a preceding hvws_route");
+    if (flags) return set_err(HVWS_EINVAL, "hvws_retain: unknown flag bits");
+    if (slot == 0 || (slot & 15u)) return set_err(HVWS_EINVAL, "hvws_retain: slot = %llu (a multiple of 16, not 0)",
+                                                  (unsigned long long)slot);
+    const uint32_t ntopics = c->rt.ntopics, nseg = c->rt.nseg;
+    if (ntopics && slot > ~0ull / ntopics)
+        return set_err(HVWS_EINVAL, "hvws_retain: %u slots of %llu bytes exceed 64 bits", ntopics, (unsigned long long)slot);
+    const uint64_t store_len = (uint64_t)ntopics * slot, ret_len = (uint64_t)ntopics * sizeof(dretained);
+    const uint8_t* dout = c->mg.dout;
+    const uint64_t out_cap = dout ? c->mg.out_cap : 0;
+    if (ntopics) {
+        if (!d_store || !d_ret) return set_err(HVWS_EINVAL, "hvws_retain: null store");
+        if ((uintptr_t)d_store & 15u) return set_err(HVWS_EINVAL, "hvws_retain: the store must be 16-byte aligned");
+        if (ranges_overlap(d_store, store_len, d_ret, ret_len) || ranges_overlap(d_store, store_len, dout, out_cap) ||
+            ranges_overlap(d_ret, ret_len, dout, out_cap))
+            return set_err(HVWS_EINVAL, "hvws_retain: the store, its entries and the message output overlap");
+    }
+    const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
+    const uint64_t np = std::min<uint64_t>(cap, ntopics) + 1;
+    HIP_OR(p.scan.ensure(retain_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(p.win.ensure((uint64_t)ntopics * 4 + 16), HVWS_ENOMEM);
+    HIP_OR(p.plan.ensure(4 * np * 8), HVWS_ENOMEM);
+    HIP_OR(p.rows.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(p.topic.ensure((cap + 1) * 4), HVWS_ENOMEM);
+    HIP_OR(p.reply.ensure((cap + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(p.first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
+    const retain_tables t{c->rt.rows.as<dtxmsg>(), c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(),
+                          c->rt.scan.as<uint32_t>(), c->rt.ev.as<dsubev>(), c->rp.scan.as<uint64_t>() + cap, cap,
+                          c->rp.first.as<uint64_t>(), c->rp.count.as<uint64_t>(), nseg, ntopics, dout, out_cap, d_store,
+                          slot, reinterpret_cast<dretained*>(d_ret)};
+    uint64_t* plan = p.plan.as<uint64_t>();
+    const retain_work w{p.win.as<uint32_t>(), p.scan.p, plan, plan + np, plan + 2 * np, plan + 3 * np,
+                        p.rows.as<dtxmsg>(), p.topic.as<uint32_t>(), p.reply.as<uint64_t>(), p.first.as<uint64_t>(),
+                        p.count.as<uint64_t>(), p.meta.as<uint64_t>()};
+    // the timed device work (hvws_last_kernel_ms): the whole pass
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_retain(t, w, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    p.nseg = nseg;
+    p.route = c->rt.seq;
+    p.rep = c->rp.seq;
+    p.msg = c->mg.seq;
+    p.gen = c->scan_gen;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_retain's snapshot tables stand: no route, reply call, message call or scan since.
+bool retain_valid(const hvws_ctx* c) {
+    return route_valid(c) && c->rn.have && c->rn.route == c->rt.seq && c->rn.rep == c->rp.seq && c->rn.msg == c->mg.seq &&
+           c->rn.gen == c->scan_gen;
+}
+int retain_ctx(hvws_ctx* c) {
+    if (int rc = check_ctx(c)) return rc;
+    return retain_valid(c) ? HVWS_OK : set_err(HVWS_EINVAL, "no hvws_retain call yet");
+}
+}  // namespace
+
+const hvws_tx_msg* hvws_retain_device(hvws_ctx* c) { return retain_valid(c) ? c->rn.rows.as<hvws_tx_msg>() : nullptr; }
+
+const uint64_t* hvws_retain_count_device(hvws_ctx* c) { return retain_valid(c) ? c->rn.meta.as<uint64_t>() : nullptr; }
+
+int64_t hvws_retain_count(hvws_ctx* c) {
+    if (retain_ctx(c)) return -1;
+    return read_count(c, c->rn.meta.as<uint64_t>(), "hvws_retain_count");
+}
+
+int hvws_get_retain(hvws_ctx* c, hvws_tx_msg* rows, uint32_t* topic, uint64_t* reply, uint64_t first, uint64_t n) {
+    const int64_t have = hvws_retain_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "snapshot range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{rows, c->rn.rows.as<dtxmsg>() + first, n * sizeof(dtxmsg)},
+                         {topic, c->rn.topic.as<uint32_t>() + first, n * 4},
+                         {reply, c->rn.reply.as<uint64_t>() + first, n * 8}});
+}
+
+int hvws_get_segment_retain(hvws_ctx* c, uint64_t* first, uint64_t* count) {
+    if (int rc = retain_ctx(c)) return rc;
+    const uint64_t nseg = c->rn.nseg;
+    return read_rows(c, {{first, c->rn.first.p, nseg * 8}, {count, c->rn.count.p, nseg * 8}});
+}
+
+int hvws_get_retain_totals(hvws_ctx* c, uint64_t out[5]) {
+    if (int rc = retain_ctx(c)) return rc;
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_retain_totals: null out");
+    return read_rows(c, {{out, c->rn.meta.as<uint64_t>() + 1, 40}});
+}
+
+uint64_t hvws_retain_tile(void) { return RETAIN_TILE; }
 
 static_assert(BF_OVER == HVWS_BF_OVER, "budget flag bits");
 

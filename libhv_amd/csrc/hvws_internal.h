@@ -702,6 +702,10 @@ struct route_work {
     uint64_t* meta;
 };
 uint64_t route_scratch_bytes(uint64_t cap);
+// The scratch begins with the count scan's result, which stands until the next
+// launch_route: four 32-bit words per reply, the {publications, subscribes,
+// unsubscribes, bad + stopped} before it (hvws_retain.hip reads the event index
+// of a SUB reply from words 1 and 2).
 // The whole pass, no wait.  No read leaves [off, off + min(len, 12)) of a reply,
 // nor out[0, out_cap).
 hipError_t launch_route(const route_tables& t, const route_work& w, hipStream_t st);
@@ -823,6 +827,64 @@ uint64_t subs_merge_words(uint32_t nseg, uint32_t nover);
 // or malformed segment, a DROP per OVER destination, the host's events;
 // meta[0..4] = those four counts and their sum.
 hipError_t launch_subs_merge(const subs_merge& t, uint64_t* scratch, dsubev* out, uint64_t* meta, hipStream_t st);
+// hvws_retain (hvws_retain.hip; include/hvws.h has the contract).  dretained
+// mirrors hvws_retained.  What its kernels read: the routed rows, topic and
+// kind per reply, the event table and the count scan's result that
+// launch_route left (rt_ex: route_scratch_bytes' note), the reply count word
+// clamped to rep_cap, the reply call's first / count per segment, the winning
+// bodies in the message call's output out[0, out_cap), and the caller's entry
+// ret[t] of a topic subscribed to and not published to this turn.  They write
+// ret[t] of every topic published to and store[t * slot, t * slot + len) of
+// every topic stored.
+struct dretained {
+    uint64_t len;
+    uint32_t flags, set;
+};
+constexpr uint64_t RETAIN_TILE = 4096;   // store bytes one workgroup of the copy covers per step
+constexpr uint64_t RETAIN_GRID = 2048;   // its largest grid: 8 workgroups per CU of a 256-CU device
+struct retain_tables {
+    const dtxmsg* rows;
+    const uint32_t* topic;
+    const uint8_t* kind;
+    const uint32_t* rt_ex;
+    const dsubev* ev;
+    const uint64_t* nrep_dev;
+    uint64_t rep_cap;
+    const uint64_t* rep_first;
+    const uint64_t* rep_count;
+    uint32_t nseg;
+    uint32_t ntopics;
+    const uint8_t* out;
+    uint64_t out_cap;
+    uint8_t* store;
+    uint64_t slot;
+    dretained* ret;
+};
+// What they write besides: win (ntopics words), scratch
+// (retain_scratch_bytes(rep_cap)), the copy plan pl_* (min(rep_cap, ntopics) + 1
+// entries each: first tile, source offset, store offset, length of every stored
+// winner, dense, in reply order), the snapshot rows with topic and reply
+// (rep_cap entries each), first / count per segment, meta (8 words): [0]
+// snapshot rows, [1..5] = stored, cleared empty, cleared oversize, bytes
+// copied, snapshot rows.
+struct retain_work {
+    uint32_t* win;
+    void* scratch;
+    uint64_t* pl_tile;
+    uint64_t* pl_src;
+    uint64_t* pl_dst;
+    uint64_t* pl_len;
+    dtxmsg* rows;
+    uint32_t* topic;
+    uint64_t* reply;
+    uint64_t* first;
+    uint64_t* count;
+    uint64_t* meta;
+};
+uint64_t retain_scratch_bytes(uint64_t cap);
+// The whole pass, no wait.  No read leaves [off & ~15, off + len rounded up to
+// 16) of a winning row, nor out[0, out_cap); nothing reads the store.
+hipError_t launch_retain(const retain_tables& t, const retain_work& w, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125
