@@ -58,6 +58,10 @@
  *                message): each topic's last publication kept in a
  *                device-resident store, and a snapshot row per subscribe of the
  *                turn for a second hvws_send_messages.
+ *   hvws_envelope  what a broker puts in front of a delivery (STOMP's
+ *                destination:, MQTT's topic name; user code in the reference):
+ *                every reply's bytes written once into a second buffer,
+ *                publications behind a line naming their topic and sender.
  *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -1240,6 +1244,100 @@ int hvws_get_retain(hvws_ctx* ctx, hvws_tx_msg* rows, uint32_t* topic, uint64_t*
 int hvws_get_segment_retain(hvws_ctx* ctx, uint64_t* first, uint64_t* count);
 int hvws_get_retain_totals(hvws_ctx* ctx, uint64_t out[5]);
 uint64_t hvws_retain_tile(void);
+
+/* ---- deliveries that name their topic and sender, device resident ------------ */
+/* hvws_route trims the command header off a publication: what is delivered is
+ * the body alone, and a connection subscribed to two topics cannot tell which
+ * one a message belongs to, nor who sent it.  hvws_envelope writes every
+ * reply's outgoing bytes once into a second device buffer d_env, publications
+ * with an envelope line in front, and leaves a row table R' over d_env, indexed
+ * like the route's.  The fan-out, the budget and the send then run unchanged
+ * over rows that point into d_env; no message byte goes to the host.  The
+ * reference has no counterpart: its onmessage is user code.
+ *
+ * The envelope line mirrors the route's grammar:
+ *   envelope = 'M' digits LF               flags == 0
+ *            | 'M' digits SP digits LF     HVWS_ENV_SENDER
+ *   digits   = "0" | [1-9][0-9]{0,9}
+ * The first number is the reply's topic, the second dest_of[s_i] of the route
+ * call, s_i being the connection the reply came from (4294967295 for a reply
+ * whose piece is none of the batch's, which the fan-out refuses).  At most
+ * HVWS_ENV_HDR_MAX bytes.  An ASCII line in front of valid UTF-8 leaves a TEXT
+ * message valid UTF-8.
+ *
+ * The rule, over the valid route's replies i = 0 .. nr - 1 in table order:
+ *   - HVWS_RK_PUB: reply i's bytes are the envelope (h'_i bytes) followed by
+ *     the body, the routed row's [off, off + len) of the message call's d_out;
+ *     R'[i] = {e_i, h'_i + len, flags, key}.  An empty body gives an envelope
+ *     alone.
+ *   - HVWS_RK_OTHER (PONG, CLOSE): the bytes are copied verbatim, at any
+ *     length; R'[i] = {e_i, len, flags, key}.
+ *   - SUB, UNSUB, BAD, STOPPED: no byte is written; R'[i] = {e_i, 0, flags,
+ *     key}.  These replies have no edge in the fan-out.
+ *   - e_0 = 0 and e_{i+1} = e_i + (bytes of reply i rounded up to 16): every
+ *     reply starts 16-byte aligned, no 16-byte chunk of d_env belongs to two
+ *     replies, and the pad bytes are never written.
+ * The outputs are functions of the input alone: the same on every run, whatever
+ * the kernels' geometry; no atomic places a row or a byte.
+ *
+ * Capacity.  hvws_envelope_bound(ctx) = out_cap + (HVWS_ENV_HDR_MAX + 15) *
+ * hvws_reply_capacity(ctx) + 16 for the valid route on ctx (out_cap: the message
+ * call's; 0 when it had no d_out), host arithmetic without a wait; 0 = no valid
+ * route, or the sum exceeds 64 bits.  Replies answer disjoint pieces, so their
+ * lengths sum to at most out_cap, and each adds at most 23 bytes of envelope
+ * and 15 of padding.  There is no overflow path and no wait.
+ *
+ * hvws_envelope runs behind hvws_route, after any of the three message forms,
+ * is asynchronous on the ctx stream and does not wait; hvws_last_kernel_ms
+ * reports it when it was the last call.  The message call's d_out must still
+ * hold that call's bytes.  It changes nothing the reply, route, fan-out, budget,
+ * retain or subs getters read and invalidates none of them.  HVWS_EINVAL,
+ * nothing launched and d_env untouched: no valid hvws_route on ctx; a flags bit
+ * other than HVWS_ENV_SENDER; d_env NULL or not 16-byte aligned; env_cap below
+ * hvws_envelope_bound; d_env[0, env_cap) overlapping the message call's
+ * d_out[0, out_cap).  Reads of a body stay inside [off, off + len) rounded
+ * outwards to 16 bytes and clipped to [0, out_cap); writes to d_env touch only
+ * [e_i, e_i + bytes) of each reply.
+ *
+ * Its tables are valid until the next hvws_envelope, hvws_route, reply call,
+ * message call or scan on ctx; every getter reports none after that
+ * (hvws_envelope_device NULL, the others HVWS_EINVAL), and
+ * hvws_fanout_enveloped / hvws_retain_enveloped are refused.  d_env itself is
+ * the caller's.  hvws_envelope_device (one row per reply; hvws_reply_capacity
+ * entries, hvws_reply_count of them written) does not wait; the others do.
+ * hvws_get_envelope: rows first .. first + n - 1, a range beyond the reply count
+ * is HVWS_EINVAL; hvws_get_envelope_totals: enveloped publications, replies
+ * copied verbatim, bytes written, bytes of d_env spanned (e_nr).
+ * hvws_envelope_tile: the bytes of d_env one workgroup of the copy covers per
+ * step (tests place body lengths around it).
+ *
+ * hvws_fanout_enveloped follows hvws_fanout_routed's contract word for word,
+ * except that the rows it delivers are R' and that it needs a valid
+ * hvws_envelope on ctx (none: HVWS_EINVAL).  It fills hvws_fanout's tables:
+ * every fan-out getter, hvws_budget, hvws_subs_update_routed and
+ * hvws_send_messages run behind it unchanged; the send gets d_payload = d_env
+ * and payload_len = env_cap, and the bound hvws_budget puts on a row's length
+ * is env_cap in place of out_cap.
+ *
+ * hvws_retain_enveloped follows hvws_retain's contract word for word, except
+ * that a winner's bytes are R'[i]'s bytes in d_env: a retained value is
+ * envelope plus body, d_ret[t].len counts both, and a snapshot names its topic
+ * by itself.  "Empty" still means an empty body (the routed row's len == 0);
+ * oversize means h' + len > slot; the overlap rule covers d_env[0, env_cap) as
+ * well as d_out; it needs a valid hvws_envelope on ctx and fills hvws_retain's
+ * tables.  hvws_retain itself is unchanged (its flag bits stay refused).
+ *  */
+#define HVWS_ENV_SENDER  1u    /* the envelope names the publisher's destination id too */
+#define HVWS_ENV_HDR_MAX 23u   /* 'M' + 10 digits + ' ' + 10 digits + LF */
+uint64_t hvws_envelope_bound(hvws_ctx* ctx);
+uint32_t hvws_envelope_tile(void);
+int hvws_envelope(hvws_ctx* ctx, uint8_t* d_env, uint64_t env_cap, uint32_t flags);
+const hvws_tx_msg* hvws_envelope_device(hvws_ctx* ctx);
+int hvws_get_envelope(hvws_ctx* ctx, hvws_tx_msg* rows, uint64_t first, uint64_t n);
+int hvws_get_envelope_totals(hvws_ctx* ctx, uint64_t out[4]);
+int hvws_fanout_enveloped(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                          uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries);
+int hvws_retain_enveloped(hvws_ctx* ctx, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags);
 
 /* ---- per-destination write limits for the fan-out, device resident ---------- */
 /* hvws_budget cuts every destination's deliveries of the last hvws_fanout at

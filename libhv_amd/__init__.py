@@ -106,6 +106,9 @@ SUB_EVENT_DTYPE = np.dtype([("op", "<u4"), ("topic", "<u4"), ("dest", "<u4")])
 assert SUB_EVENT_DTYPE.itemsize == 12
 # HVWS_ROUTE_*, HVWS_RK_* and HVWS_RT_BAD (hvws_route)
 ROUTE_HDR_MAX = 12
+# hvws_envelope
+ENV_SENDER = 1
+ENV_HDR_MAX = 23
 RK_OTHER, RK_PUB, RK_SUB, RK_UNSUB, RK_BAD, RK_STOPPED = 0, 1, 2, 3, 4, 5
 RT_BAD = 1
 ROUTE_NONE = (1 << 64) - 1
@@ -284,6 +287,20 @@ _SIGS = {
     "hvws_get_segment_retain": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hvws_get_retain_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "hvws_retain_tile": (ctypes.c_uint64, []),
+    "hvws_envelope_bound": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "hvws_envelope_tile": (ctypes.c_uint32, []),
+    "hvws_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),
+    "hvws_envelope_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_get_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "hvws_get_envelope_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_fanout_enveloped": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+         ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "hvws_retain_enveloped": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32]
+    ),
     "hvws_budget": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
     ),
@@ -975,6 +992,67 @@ class Engine:
         out = (ctypes.c_uint64 * 5)()
         _check(lib().hvws_get_retain_totals(self.ctx, out), "hvws_get_retain_totals")
         return tuple(int(x) for x in out)
+
+    def envelope_bound(self) -> int:
+        """hvws_envelope_bound: the env_cap envelope() needs behind the last route()
+        call (0: there is none).  No wait."""
+        return int(lib().hvws_envelope_bound(self.ctx))
+
+    def envelope(self, env, env_cap: int, flags: int = 0) -> None:
+        """hvws_envelope behind the last route() call: every reply's outgoing bytes
+        written once into env (a DeviceBuffer or a device address, 16-byte
+        aligned, env_cap >= envelope_bound() bytes), publications behind the line
+        'M<topic>\n' (ENV_SENDER: 'M<topic> <sender>\n'), each reply 16-byte
+        aligned.  No wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_envelope(self.ctx, dev(env), env_cap, flags), "hvws_envelope")
+
+    def envelope_device(self) -> Tuple[int, int, int]:
+        """(table address, count word address, the reply capacity): msgs, d_n and n
+        of a send_messages() over the last envelope() call's rows; (None, None, 0)
+        when there is none."""
+        L = lib()
+        t = L.hvws_envelope_device(self.ctx)
+        return (t, L.hvws_reply_count_device(self.ctx), int(L.hvws_reply_capacity(self.ctx))) if t else (None, None, 0)
+
+    def envelope_table(self) -> np.ndarray:
+        """The enveloped rows [TX_MSG_DTYPE] over env, one per reply of the last
+        envelope() call."""
+        L = lib()
+        if not L.hvws_envelope_device(self.ctx):
+            _check(-2, "hvws_get_envelope")
+        n = L.hvws_reply_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_reply_count")
+        rows = np.zeros(n, dtype=TX_MSG_DTYPE)
+        _check(L.hvws_get_envelope(self.ctx, rows.ctypes.data, 0, n), "hvws_get_envelope")
+        return rows
+
+    def envelope_totals(self) -> Tuple[int, int, int, int]:
+        """(enveloped publications, replies copied verbatim, bytes written, bytes of
+        env spanned) of the last envelope() call."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hvws_get_envelope_totals(self.ctx, out), "hvws_get_envelope_totals")
+        return tuple(int(x) for x in out)
+
+    def fanout_enveloped(self, topic_first, member, nmember: int, flags: int = 0,
+                         max_deliveries: int = (1 << 64) - 1) -> int:
+        """hvws_fanout_enveloped: fanout_routed() delivering the rows of the last
+        envelope() call.  The send_messages() that follows takes env and env_cap
+        as its payload."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        n = ctypes.c_uint64(0)
+        rc = lib().hvws_fanout_enveloped(self.ctx, dev(topic_first), dev(member), nmember, flags, max_deliveries,
+                                         ctypes.byref(n))
+        self.last_deliveries = int(n.value)
+        _check(rc, "hvws_fanout_enveloped")
+        return int(n.value)
+
+    def retain_enveloped(self, store, slot: int, ret, flags: int = 0) -> None:
+        """hvws_retain_enveloped: retain() keeping the last envelope() call's bytes,
+        envelope and body, so that a snapshot names its topic.  No wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_retain_enveloped(self.ctx, dev(store), slot, dev(ret), flags), "hvws_retain_enveloped")
 
     def budget(self, budget, budget_all: int = (1 << 64) - 1, fragment: int = 0, masked: bool = False) -> None:
         """hvws_budget over the last fanout() call: every destination's deliveries

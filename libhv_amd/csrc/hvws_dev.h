@@ -93,6 +93,25 @@ __device__ __forceinline__ u32x4 funnel16(u32x4 a, u32x4 b, uint32_t s) {
     return u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
 }
 
+// Bytes [s, s + n) of out, n in 1 .. 16, as the low bytes of a 16-byte value.
+// No load leaves [s & ~15, s + n rounded up to 16), nor [0, out_cap)
+// (hvws_retain.hip, hvws_envelope.hip).
+__device__ __forceinline__ u32x4 ld16_clipped(const uint8_t* __restrict__ out, uint64_t out_cap, uint64_t s, uint32_t n) {
+    const uint64_t a = s & ~15ull;
+    const uint32_t sft = (uint32_t)(s & 15u);
+    const bool two = sft + n > 16u;
+    if (a + (two ? 32u : 16u) <= out_cap) {
+        const u32x4 va = *reinterpret_cast<const u32x4*>(out + a);
+        const u32x4 vb = two ? *reinterpret_cast<const u32x4*>(out + a + 16) : va;
+        return sft ? funnel16(va, vb, sft) : va;
+    }
+    uint32_t wd[4] = {0, 0, 0, 0};   // the buffer ends inside the chunk's lines: byte by byte
+#pragma unroll
+    for (uint32_t b = 0; b < 16; ++b)
+        if (b < n && s + b < out_cap) wd[b >> 2] |= (uint32_t)out[s + b] << (8u * (b & 3u));
+    return u32x4{wd[0], wd[1], wd[2], wd[3]};
+}
+
 // OR bytes [0, b1 - b0) of the 16-byte little-endian value (vlo, vhi) into
 // bytes [b0, b1) of the chunk (olo, ohi); 0 <= b0 < b1 <= 16.
 __device__ __forceinline__ void put_bytes(uint64_t& olo, uint64_t& ohi, uint64_t vlo, uint64_t vhi, uint32_t b0,

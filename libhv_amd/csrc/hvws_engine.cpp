@@ -274,7 +274,8 @@ struct pass_replies {
 // its histograms, the delivery table and the reply of each delivery,
 // per-destination first / count.  rep / msg: the reply call (pass_replies::seq)
 // and the message call (pass_msg::seq) it expanded.  key_in: which of ping /
-// pong holds the sorted keys (hvws_budget reads them).
+// pong holds the sorted keys (hvws_budget reads them).  maxlen: the bound on a
+// row's length hvws_budget takes (hvws_fanout_enveloped: its env_cap).
 struct pass_fan {
     dbuf scan, in, seg, meta, ping, pong, hist, msgs, reply, first, count;
     up_slot up;
@@ -282,6 +283,7 @@ struct pass_fan {
     uint32_t ndest = 0;
     uint64_t n = 0;   // deliveries
     uint64_t rep = 0, msg = 0;
+    uint64_t maxlen = 0;
     int key_in = 0;
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&scan, &in, &seg, &meta, &ping, &pong, &hist, &msgs, &reply, &first, &count});
@@ -322,6 +324,24 @@ struct pass_retain {
     uint64_t route = 0, rep = 0, msg = 0, gen = 0;
     void release(rel ph) {
         if (ph == REL_DEVICE) free_all({&scan, &win, &plan, &rows, &topic, &reply, &first, &count, &meta});
+    }
+};
+
+// hvws_envelope: the plan scan's scratch, the enveloped rows (and their twin
+// for hvws_retain_enveloped), the copy plan (four arrays in one buffer),
+// {enveloped publications, replies copied verbatim, bytes written, bytes of
+// d_env spanned}.  Nothing goes up: no slot.  d_env is the caller's.  route /
+// rep / msg / gen: the route call (pass_route::seq), the reply call, the message
+// call and the scans it ran behind; env / env_cap / flags: its arguments.
+struct pass_envelope {
+    dbuf scan, rows, rrows, plan, meta;
+    bool have = false;
+    uint8_t* env = nullptr;
+    uint64_t env_cap = 0;
+    uint32_t flags = 0;
+    uint64_t route = 0, rep = 0, msg = 0, gen = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &rows, &rrows, &plan, &meta});
     }
 };
 
@@ -495,6 +515,7 @@ struct hvws_ctx {
     pass_fan fan;
     pass_route rt;
     pass_retain rn;
+    pass_envelope en;
     pass_budget bg;
     pass_subs subs;
     pass_check ck;
@@ -2572,6 +2593,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->fan.release(ph);
         c->rt.release(ph);
         c->rn.release(ph);
+        c->en.release(ph);
         c->bg.release(ph);
         c->subs.release(ph);
         c->ck.release(ph);
@@ -4001,6 +4023,7 @@ int fan_run(hvws_ctx* c, const char* who, const fan_tables& t, uint64_t per, uin
     c->fan.n = ndel;
     c->fan.rep = c->rp.seq;
     c->fan.msg = c->mg.seq;
+    c->fan.maxlen = c->mg.out_cap;   // the rows point into the message call's output
     return HVWS_OK;
 }
 
@@ -4180,30 +4203,29 @@ bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
 }
 }  // namespace
 
-// Each topic's last publication of the turn into the caller's store, and the
-// snapshot rows for the turn's subscribes (hvws_retain.hip): the pick, one
-// scan, the finish, the copy.  No wait.
-int hvws_retain(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
+namespace {
+// What hvws_retain and hvws_retain_enveloped share once the route (and the
+// envelope) is known to stand: rows / src[0, src_cap) are the winners' rows and
+// the buffer they point into; the message call's output may not overlap the
+// store either way.
+int retain_run(hvws_ctx* c, const char* who, const dtxmsg* rows, const uint8_t* src, uint64_t src_cap, uint8_t* d_store,
+               uint64_t slot, hvws_retained* d_ret) {
     pass_retain& p = c->rn;
-    p.have = false;   // the tables are being rewritten
-    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_retain without a preceding hvws_route");
-    if (flags) return set_err(HVWS_EINVAL, "hvws_retain: unknown flag bits");
-    if (slot == 0 || (slot & 15u)) return set_err(HVWS_EINVAL, "hvws_retain: slot = %llu (a multiple of 16, not 0)",
+    if (slot == 0 || (slot & 15u)) return set_err(HVWS_EINVAL, "%s: slot = %llu (a multiple of 16, not 0)", who,
                                                   (unsigned long long)slot);
     const uint32_t ntopics = c->rt.ntopics, nseg = c->rt.nseg;
     if (ntopics && slot > ~0ull / ntopics)
-        return set_err(HVWS_EINVAL, "hvws_retain: %u slots of %llu bytes exceed 64 bits", ntopics, (unsigned long long)slot);
+        return set_err(HVWS_EINVAL, "%s: %u slots of %llu bytes exceed 64 bits", who, ntopics, (unsigned long long)slot);
     const uint64_t store_len = (uint64_t)ntopics * slot, ret_len = (uint64_t)ntopics * sizeof(dretained);
     const uint8_t* dout = c->mg.dout;
     const uint64_t out_cap = dout ? c->mg.out_cap : 0;
     if (ntopics) {
-        if (!d_store || !d_ret) return set_err(HVWS_EINVAL, "hvws_retain: null store");
-        if ((uintptr_t)d_store & 15u) return set_err(HVWS_EINVAL, "hvws_retain: the store must be 16-byte aligned");
+        if (!d_store || !d_ret) return set_err(HVWS_EINVAL, "%s: null store", who);
+        if ((uintptr_t)d_store & 15u) return set_err(HVWS_EINVAL, "%s: the store must be 16-byte aligned", who);
         if (ranges_overlap(d_store, store_len, d_ret, ret_len) || ranges_overlap(d_store, store_len, dout, out_cap) ||
-            ranges_overlap(d_ret, ret_len, dout, out_cap))
-            return set_err(HVWS_EINVAL, "hvws_retain: the store, its entries and the message output overlap");
+            ranges_overlap(d_ret, ret_len, dout, out_cap) || ranges_overlap(d_store, store_len, src, src_cap) ||
+            ranges_overlap(d_ret, ret_len, src, src_cap))
+            return set_err(HVWS_EINVAL, "%s: the store, its entries and the message output overlap", who);
     }
     const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
     const uint64_t np = std::min<uint64_t>(cap, ntopics) + 1;
@@ -4216,9 +4238,9 @@ int hvws_retain(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_r
     HIP_OR(p.first.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     HIP_OR(p.count.ensure((uint64_t)nseg * 8 + 16), HVWS_ENOMEM);
     HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
-    const retain_tables t{c->rt.rows.as<dtxmsg>(), c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(),
+    const retain_tables t{rows, c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(),
                           c->rt.scan.as<uint32_t>(), c->rt.ev.as<dsubev>(), c->rp.scan.as<uint64_t>() + cap, cap,
-                          c->rp.first.as<uint64_t>(), c->rp.count.as<uint64_t>(), nseg, ntopics, dout, out_cap, d_store,
+                          c->rp.first.as<uint64_t>(), c->rp.count.as<uint64_t>(), nseg, ntopics, src, src_cap, d_store,
                           slot, reinterpret_cast<dretained*>(d_ret)};
     uint64_t* plan = p.plan.as<uint64_t>();
     const retain_work w{p.win.as<uint32_t>(), p.scan.p, plan, plan + np, plan + 2 * np, plan + 3 * np,
@@ -4235,6 +4257,20 @@ int hvws_retain(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_r
     p.msg = c->mg.seq;
     p.gen = c->scan_gen;
     return HVWS_OK;
+}
+}  // namespace
+
+// Each topic's last publication of the turn into the caller's store, and the
+// snapshot rows for the turn's subscribes (hvws_retain.hip): the pick, one
+// scan, the finish, the copy.  No wait.
+int hvws_retain(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    c->rn.have = false;   // the tables are being rewritten
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_retain without a preceding hvws_route");
+    if (flags) return set_err(HVWS_EINVAL, "hvws_retain: unknown flag bits");
+    const uint8_t* dout = c->mg.dout;
+    return retain_run(c, "hvws_retain", c->rt.rows.as<dtxmsg>(), dout, dout ? c->mg.out_cap : 0, d_store, slot, d_ret);
 }
 
 namespace {
@@ -4282,6 +4318,130 @@ int hvws_get_retain_totals(hvws_ctx* c, uint64_t out[5]) {
 
 uint64_t hvws_retain_tile(void) { return RETAIN_TILE; }
 
+static_assert(HVWS_ENV_HDR_MAX == 23 && ENV_TILE <= 0xFFFFFFFFull, "envelope constants");
+
+namespace {
+// out_cap + (HVWS_ENV_HDR_MAX + 15) * reply capacity + 16 (include/hvws.h); 0 where 64 bits do not hold it
+uint64_t envelope_bound(const hvws_ctx* c) {
+    const uint64_t out_cap = c->mg.dout ? c->mg.out_cap : 0, cap = c->rp.cap;   // cap < 2^32 - 1: hvws_route saw it
+    const uint64_t per = (HVWS_ENV_HDR_MAX + 15u) * cap + 16u;
+    return out_cap > ~0ull - per ? 0 : out_cap + per;
+}
+}  // namespace
+
+uint64_t hvws_envelope_bound(hvws_ctx* c) { return route_valid(c) ? envelope_bound(c) : 0; }
+
+uint32_t hvws_envelope_tile(void) { return (uint32_t)ENV_TILE; }
+
+// Every reply's outgoing bytes into the caller's second buffer, publications
+// behind their envelope line, and the rows that point there
+// (hvws_envelope.hip): one scan, the finish, the copy.  No wait.
+int hvws_envelope(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    pass_envelope& p = c->en;
+    p.have = false;   // the tables are being rewritten
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_envelope without a preceding hvws_route");
+    if (flags & ~(uint32_t)HVWS_ENV_SENDER) return set_err(HVWS_EINVAL, "hvws_envelope: unknown flag bits");
+    if (!d_env || ((uintptr_t)d_env & 15u)) return set_err(HVWS_EINVAL, "hvws_envelope: d_env must be 16-byte aligned, not null");
+    const uint64_t bound = envelope_bound(c);
+    if (bound == 0 || env_cap < bound)
+        return set_err(HVWS_EINVAL, "hvws_envelope: env_cap = %llu, hvws_envelope_bound %llu", (unsigned long long)env_cap,
+                       (unsigned long long)bound);
+    const uint8_t* dout = c->mg.dout;
+    const uint64_t out_cap = dout ? c->mg.out_cap : 0;
+    if (ranges_overlap(d_env, env_cap, dout, out_cap))
+        return set_err(HVWS_EINVAL, "hvws_envelope: d_env and the message output overlap");
+    const uint64_t cap = c->rp.cap, np = cap + 1;
+    HIP_OR(p.scan.ensure(env_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(p.rows.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(p.rrows.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
+    HIP_OR(p.plan.ensure(4 * np * 8), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
+    const env_tables t{c->rt.rows.as<dtxmsg>(), c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(),
+                       c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap, c->mg.msgs.as<dmsg>(),
+                       c->mg.meta.as<uint64_t>(), c->mg.cap, c->rt.nseg, c->rt.in.as<uint32_t>(), dout, out_cap, d_env,
+                       env_cap, (flags & HVWS_ENV_SENDER) != 0};
+    uint64_t* plan = p.plan.as<uint64_t>();
+    const env_work w{p.scan.p, p.rows.as<dtxmsg>(), p.rrows.as<dtxmsg>(), plan, plan + np, plan + 2 * np, plan + 3 * np,
+                     p.meta.as<uint64_t>()};
+    // the timed device work (hvws_last_kernel_ms): the whole pass
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_envelope(t, w, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    p.env = d_env;
+    p.env_cap = env_cap;
+    p.flags = flags;
+    p.route = c->rt.seq;
+    p.rep = c->rp.seq;
+    p.msg = c->mg.seq;
+    p.gen = c->scan_gen;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_envelope's tables stand: no route, reply call, message call or scan since.
+bool envelope_valid(const hvws_ctx* c) {
+    return route_valid(c) && c->en.have && c->en.route == c->rt.seq && c->en.rep == c->rp.seq && c->en.msg == c->mg.seq &&
+           c->en.gen == c->scan_gen;
+}
+int envelope_ctx(hvws_ctx* c) {
+    if (int rc = check_ctx(c)) return rc;
+    return envelope_valid(c) ? HVWS_OK : set_err(HVWS_EINVAL, "no hvws_envelope call yet");
+}
+}  // namespace
+
+const hvws_tx_msg* hvws_envelope_device(hvws_ctx* c) { return envelope_valid(c) ? c->en.rows.as<hvws_tx_msg>() : nullptr; }
+
+int hvws_get_envelope(hvws_ctx* c, hvws_tx_msg* rows, uint64_t first, uint64_t n) {
+    if (int rc = envelope_ctx(c)) return rc;
+    const int64_t have = hvws_reply_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "reply range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{rows, c->en.rows.as<dtxmsg>() + first, n * sizeof(dtxmsg)}});
+}
+
+int hvws_get_envelope_totals(hvws_ctx* c, uint64_t out[4]) {
+    if (int rc = envelope_ctx(c)) return rc;
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_envelope_totals: null out");
+    return read_rows(c, {{out, c->en.meta.as<uint64_t>(), 32}});
+}
+
+// hvws_fanout_routed delivering the rows of the last hvws_envelope.
+int hvws_fanout_enveloped(hvws_ctx* c, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
+                          uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (out_deliveries) *out_deliveries = 0;
+    c->fan.have = false;   // the tables are being rewritten
+    c->bg.have = false;    // ... which a budget pass ran over
+    if (!envelope_valid(c)) return set_err(HVWS_EINVAL, "hvws_fanout_enveloped without a preceding hvws_envelope");
+    if (flags & ~(uint32_t)HVWS_FAN_SELF) return set_err(HVWS_EINVAL, "hvws_fanout_enveloped: unknown flag bits");
+    if (c->rt.ntopics && (!d_topic_first || (!d_member && nmember)))
+        return set_err(HVWS_EINVAL, "hvws_fanout_enveloped: null subscription table");
+    const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
+    const fan_tables t{c->en.rows.as<dtxmsg>(), c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap,
+                       c->mg.msgs.as<dmsg>(), c->mg.meta.as<uint64_t>(), c->mg.cap, c->rt.nseg, c->rt.in.as<uint32_t>(),
+                       nullptr, d_topic_first, d_member, c->rt.ntopics, nmember, c->rt.ndest,
+                       (flags & HVWS_FAN_SELF) != 0, c->rt.topic.as<uint32_t>()};
+    if ((rc = fan_run(c, "hvws_fanout_enveloped", t, cap, max_deliveries, out_deliveries)) != HVWS_OK) return rc;
+    c->fan.maxlen = c->en.env_cap;   // the rows point into d_env
+    return HVWS_OK;
+}
+
+// hvws_retain keeping the enveloped bytes: the winners' rows are the envelope
+// pass's (length 0 where the body is empty), their bytes are in d_env.
+int hvws_retain_enveloped(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    c->rn.have = false;   // the tables are being rewritten
+    if (!envelope_valid(c)) return set_err(HVWS_EINVAL, "hvws_retain_enveloped without a preceding hvws_envelope");
+    if (flags) return set_err(HVWS_EINVAL, "hvws_retain_enveloped: unknown flag bits");
+    return retain_run(c, "hvws_retain_enveloped", c->en.rrows.as<dtxmsg>(), c->en.env, c->en.env_cap, d_store, slot, d_ret);
+}
+
 static_assert(BF_OVER == HVWS_BF_OVER, "budget flag bits");
 
 // The last hvws_fanout's deliveries cut at every destination's byte budget
@@ -4297,9 +4457,10 @@ int hvws_budget(hvws_ctx* c, const uint64_t* d_budget, uint64_t budget_all, uint
     const uint64_t n = c->fan.n;
     const uint32_t ndest = c->fan.ndest;
     const uint64_t F = fragment ? fragment : 0xFFFFu;   // WebSocketChannel.cpp:6
-    // no row names more than the message call's out_cap bytes: n messages of that
+    // no row names more than the bytes of the buffer it points into (the message
+    // call's out_cap; env_cap behind hvws_fanout_enveloped): n messages of that
     // length bound every sum the kernels form
-    const uint64_t maxlen = c->mg.out_cap, wmax = budget_wire(maxlen, F, masked);
+    const uint64_t maxlen = c->fan.maxlen, wmax = budget_wire(maxlen, F, masked);
     if (n && (wmax == ~0ull || wmax > ~0ull / n))
         return set_err(HVWS_EINVAL, "hvws_budget: %llu deliveries of up to %llu bytes do not fit 64 bits",
                        (unsigned long long)n, (unsigned long long)wmax);

@@ -885,6 +885,53 @@ uint64_t retain_scratch_bytes(uint64_t cap);
 // The whole pass, no wait.  No read leaves [off & ~15, off + len rounded up to
 // 16) of a winning row, nor out[0, out_cap); nothing reads the store.
 hipError_t launch_retain(const retain_tables& t, const retain_work& w, hipStream_t st);
+// hvws_envelope (hvws_envelope.hip; include/hvws.h has the contract).  What its
+// kernels read: the routed rows, topic and kind per reply that launch_route
+// left, the reply count word clamped to rep_cap, with `sender` the piece each
+// reply answers, the piece table and dest_of per segment (device), and the
+// bodies in the message call's output out[0, out_cap).  They write env[0,
+// env_cap): reply i's bytes at its offset e_i, nothing between replies.
+constexpr uint64_t ENV_TILE = 1024;   // bytes of env one workgroup of the copy (one wave) covers per step
+constexpr uint64_t ENV_GRID = 8192;   // its largest grid: 32 waves per CU of a 256-CU device
+struct env_tables {
+    const dtxmsg* rows;
+    const uint32_t* topic;
+    const uint8_t* kind;
+    const uint64_t* piece;
+    const uint64_t* nrep_dev;
+    uint64_t rep_cap;
+    const dmsg* pieces;
+    const uint64_t* mg_meta;
+    uint64_t piece_cap;
+    uint32_t nseg;
+    const uint32_t* dest_of;
+    const uint8_t* out;
+    uint64_t out_cap;
+    uint8_t* env;
+    uint64_t env_cap;
+    bool sender;   // HVWS_ENV_SENDER
+};
+// What they write besides: scratch (env_scratch_bytes(rep_cap)), the enveloped
+// rows (rep_cap entries; rrows: the same with length 0 where a publication's
+// body is empty, the rows launch_retain takes), the copy plan pl_* (rep_cap + 1 entries each: first
+// tile, source offset, offset in env and length of every body copied, dense, in
+// reply order), meta (8 words): [0..3] = enveloped publications, replies copied
+// verbatim, bytes written, bytes of env spanned.
+struct env_work {
+    void* scratch;
+    dtxmsg* rows;
+    dtxmsg* rrows;
+    uint64_t* pl_tile;
+    uint64_t* pl_src;
+    uint64_t* pl_dst;
+    uint64_t* pl_len;
+    uint64_t* meta;
+};
+uint64_t env_scratch_bytes(uint64_t cap);
+// The whole pass, no wait.  No read leaves [off & ~15, off + len rounded up to
+// 16) of a copied row, nor out[0, out_cap); no write leaves reply i's [e_i, e_i +
+// bytes), nor env[0, env_cap).
+hipError_t launch_envelope(const env_tables& t, const env_work& w, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125

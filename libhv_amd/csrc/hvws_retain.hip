@@ -173,24 +173,6 @@ __global__ __launch_bounds__(256) void k_retain_finish(retain_tables in, retain_
     }
 }
 
-// Bytes [s, s + n) of out, n in 1 .. 16, as the low bytes of a 16-byte value.
-// No load leaves [s & ~15, s + n rounded up to 16), nor [0, out_cap).
-__device__ __forceinline__ u32x4 retain_load16(const uint8_t* __restrict__ out, uint64_t out_cap, uint64_t s, uint32_t n) {
-    const uint64_t a = s & ~15ull;
-    const uint32_t sft = (uint32_t)(s & 15u);
-    const bool two = sft + n > 16u;
-    if (a + (two ? 32u : 16u) <= out_cap) {
-        const u32x4 va = *reinterpret_cast<const u32x4*>(out + a);
-        const u32x4 vb = two ? *reinterpret_cast<const u32x4*>(out + a + 16) : va;
-        return sft ? funnel16(va, vb, sft) : va;
-    }
-    uint32_t wd[4] = {0, 0, 0, 0};   // the buffer ends inside the chunk's lines: byte by byte
-#pragma unroll
-    for (uint32_t b = 0; b < 16; ++b)
-        if (b < n && s + b < out_cap) wd[b >> 2] |= (uint32_t)out[s + b] << (8u * (b & 3u));
-    return u32x4{wd[0], wd[1], wd[2], wd[3]};
-}
-
 // The copy of the winning bodies into their slots, by destination tile (file
 // comment).  total: the plan scan's total; pl_tile[0 .. stored]: the first tile
 // of each stored winner and, behind the last, the tile count.
@@ -226,7 +208,7 @@ __global__ __launch_bounds__(RETAIN_T) void k_retain_copy(const uint8_t* __restr
         const uint64_t c = (g - first) * RETAIN_TILE + (uint64_t)threadIdx.x * 16u;
         if (c >= len) continue;
         const uint32_t n = len - c < 16 ? (uint32_t)(len - c) : 16u;
-        const u32x4 v = retain_load16(out, out_cap, src + c, n);
+        const u32x4 v = ld16_clipped(out, out_cap, src + c, n);
         uint8_t* d = store + dst + c;
         if (n == 16) {
             *reinterpret_cast<u32x4*>(d) = v;
