@@ -62,6 +62,12 @@
  *                destination:, MQTT's topic name; user code in the reference):
  *                every reply's bytes written once into a second buffer,
  *                publications behind a line naming their topic and sender.
+ *   hvws_sequence  what a broker's stream position is (MQTT's packet id, a
+ *                log's offset; user code in the reference): every publication
+ *                numbered within its topic from counters kept on the device.
+ *   hvws_envelope_sequenced  hvws_envelope with that number on the line, so
+ *                that a subscriber sees what hvws_budget cut and can order a
+ *                retained snapshot against the live deliveries behind it.
  *   hvws_check  what the reference leaves out altogether: failing a connection
  *                that breaks the protocol (RFC 6455 sec. 7.1.7) -- the failing
  *                record and close code per connection, on the device; opt-in.
@@ -1338,6 +1344,99 @@ int hvws_get_envelope_totals(hvws_ctx* ctx, uint64_t out[4]);
 int hvws_fanout_enveloped(hvws_ctx* ctx, const uint64_t* d_topic_first, const uint32_t* d_member, uint64_t nmember,
                           uint32_t flags, uint64_t max_deliveries, uint64_t* out_deliveries);
 int hvws_retain_enveloped(hvws_ctx* ctx, uint8_t* d_store, uint64_t slot, hvws_retained* d_ret, uint32_t flags);
+
+/* ---- per-topic sequence numbers in the envelope, device resident ------------- */
+/* hvws_budget drops a slow destination's deliveries, and a snapshot of
+ * hvws_retain cannot be related to the live deliveries that follow it: a
+ * subscriber cannot tell that it missed a message.  hvws_sequence gives every
+ * publication of the turn the next number of its topic's stream;
+ * hvws_envelope_sequenced is hvws_envelope with that number on the line.  The
+ * reference has no counterpart: its onmessage is user code.
+ *
+ * The counters.  d_seq is the caller's device memory, ntopics words of 8 bytes
+ * (ntopics: the valid hvws_route's), kept across turns like hvws_retain's
+ * d_ret.  d_seq[t] is the last number given out in topic t; the caller seeds it
+ * (hvws_memset to 0, or its own values after a restart).
+ *
+ * The rule, over the valid route's replies i = 0 .. nr - 1 in table order:
+ *   - a reply of kind HVWS_RK_PUB to topic t gets
+ *       seq[i] = d_seq_before[t] + 1 + #{ j < i : kind[j] == PUB, topic[j] == t }
+ *     modulo 2^64 (a counter at 2^64 - 1 gives 0 next);
+ *   - after the call d_seq[t] = d_seq_before[t] + #{ PUB replies to t };
+ *   - every other kind (OTHER, SUB, UNSUB, BAD, STOPPED) gets seq[i] = 0 and
+ *     takes no number.  A PUB is told from the rest by its kind, not by
+ *     seq != 0;
+ *   - a topic without a publication this turn is neither read nor written;
+ *   - numbers follow table order: behind hvws_messages_rfc each connection's
+ *     stream order, connections in segment order;
+ *   - whether hvws_budget later cuts a delivery does not matter: the hole that
+ *     leaves in what a destination receives is the purpose.
+ * The outputs are functions of the input alone: no atomic decides a number.
+ *
+ * hvws_sequence runs behind hvws_route, after any of the three message forms, is
+ * asynchronous on the ctx stream and does not wait; hvws_last_kernel_ms reports
+ * it when it was the last call.  It touches no payload byte, changes nothing the
+ * reply, route, fan-out, budget, retain, envelope or subs getters read and
+ * invalidates none of them.  It reads topic and kind per reply of the route and
+ * d_seq[t] of the topics published to; it writes those d_seq[t] and its own
+ * table.
+ *
+ * A turn is numbered once: a second hvws_sequence behind the same hvws_route is
+ * HVWS_EINVAL and leaves the counters and the first call's table as they are (a
+ * retry would skip numbers); the next hvws_route re-arms it.  HVWS_EINVAL,
+ * nothing launched and the counters untouched, besides: no valid hvws_route on
+ * ctx; a flags bit set (none is defined); with ntopics > 0, d_seq NULL or not
+ * 8-byte aligned; d_seq[0, ntopics) overlapping the message call's
+ * d_out[0, out_cap).  With ntopics == 0 the call succeeds and numbers nothing
+ * (d_seq may be NULL).
+ *
+ * Its table is valid until the next hvws_sequence that is not refused as a
+ * repeat, hvws_route, reply call, message call or scan on ctx; after that
+ * hvws_sequence_device returns NULL, the getters HVWS_EINVAL, and
+ * hvws_envelope_sequenced is refused.  hvws_sequence_device (seq per reply,
+ * hvws_reply_capacity entries, 0 behind the reply count) does not wait; the
+ * others do.  hvws_get_sequence: seq first .. first + n - 1, a range beyond the
+ * reply count is HVWS_EINVAL; hvws_get_sequence_totals: publications numbered,
+ * distinct topics published to.
+ *
+ * hvws_envelope_sequenced follows hvws_envelope's contract word for word --
+ * offsets e_i, 16-byte alignment, verbatim PONG / CLOSE, rows of length 0 for
+ * SUB / UNSUB / BAD / STOPPED, read and write bounds, the overlap rule, flags 0
+ * or HVWS_ENV_SENDER -- except that
+ *   - a publication's line carries its number:
+ *       envelope = 'M' digits SP '#' seq LF              flags == 0
+ *                | 'M' digits SP digits SP '#' seq LF    HVWS_ENV_SENDER
+ *       seq      = "0" | [1-9][0-9]{0,19}
+ *     seq being seq[i] of the valid hvws_sequence in decimal; at most
+ *     HVWS_SEQ_HDR_MAX bytes.  The '#' keeps the two forms and hvws_envelope's
+ *     own apart for a client's parser;
+ *   - it needs a valid hvws_sequence on ctx (none: HVWS_EINVAL, d_env
+ *     untouched);
+ *   - env_cap is checked against hvws_envelope_sequenced_bound(ctx) = out_cap +
+ *     (HVWS_SEQ_HDR_MAX + 15) * hvws_reply_capacity(ctx) + 16 (0 as
+ *     hvws_envelope_bound);
+ *   - it reads the number per reply besides.
+ * It fills hvws_envelope's tables: hvws_envelope_device, hvws_get_envelope,
+ * hvws_get_envelope_totals, hvws_fanout_enveloped and hvws_retain_enveloped,
+ * and hvws_budget, hvws_subs_update_routed and hvws_send_messages behind them,
+ * run unchanged.  A retained value is then line plus body: a snapshot tells the
+ * joiner the number it holds, and the joiner expects that number + 1 next in the
+ * topic.  hvws_envelope itself is unchanged (its other flag bits stay refused).
+ *
+ * Gap detection on the client.  A subscriber that saw n in a topic and then
+ * n + 2 missed n + 1 -- unless n + 1 was its own publication: without
+ * HVWS_FAN_SELF a publisher is not delivered its own messages, which take
+ * numbers it does not otherwise see, and there is no acknowledgement row that
+ * tells a publisher the number it was given.  A client that wants gap detection
+ * must either be served with HVWS_FAN_SELF or learn from the application which
+ * numbers its own publications took.   */
+#define HVWS_SEQ_HDR_MAX 45u   /* 'M' + 10 digits + ' ' + 10 digits + ' ' + '#' + 20 digits + LF */
+int hvws_sequence(hvws_ctx* ctx, uint64_t* d_seq, uint32_t flags);
+const uint64_t* hvws_sequence_device(hvws_ctx* ctx);
+int hvws_get_sequence(hvws_ctx* ctx, uint64_t* seq, uint64_t first, uint64_t n);
+int hvws_get_sequence_totals(hvws_ctx* ctx, uint64_t out[2]);
+uint64_t hvws_envelope_sequenced_bound(hvws_ctx* ctx);
+int hvws_envelope_sequenced(hvws_ctx* ctx, uint8_t* d_env, uint64_t env_cap, uint32_t flags);
 
 /* ---- per-destination write limits for the fan-out, device resident ---------- */
 /* hvws_budget cuts every destination's deliveries of the last hvws_fanout at

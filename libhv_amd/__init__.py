@@ -109,6 +109,8 @@ ROUTE_HDR_MAX = 12
 # hvws_envelope
 ENV_SENDER = 1
 ENV_HDR_MAX = 23
+# hvws_envelope_sequenced
+SEQ_HDR_MAX = 45
 RK_OTHER, RK_PUB, RK_SUB, RK_UNSUB, RK_BAD, RK_STOPPED = 0, 1, 2, 3, 4, 5
 RT_BAD = 1
 ROUTE_NONE = (1 << 64) - 1
@@ -301,6 +303,12 @@ _SIGS = {
     "hvws_retain_enveloped": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32]
     ),
+    "hvws_sequence": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "hvws_sequence_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "hvws_get_sequence": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "hvws_get_sequence_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "hvws_envelope_sequenced_bound": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "hvws_envelope_sequenced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),
     "hvws_budget": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
     ),
@@ -1053,6 +1061,49 @@ class Engine:
         envelope and body, so that a snapshot names its topic.  No wait."""
         dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         _check(lib().hvws_retain_enveloped(self.ctx, dev(store), slot, dev(ret), flags), "hvws_retain_enveloped")
+
+    def sequence(self, seq_buf, flags: int = 0) -> None:
+        """hvws_sequence behind the last route() call: every publication of the turn
+        gets the next number of its topic, in table order.  seq_buf: the counters,
+        ntopics words of 8 bytes in device memory (a DeviceBuffer or a device
+        address), kept across turns; seq_buf[t] is the last number given out in
+        topic t.  A turn is numbered once.  No wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_sequence(self.ctx, dev(seq_buf), flags), "hvws_sequence")
+
+    def sequence_table(self) -> np.ndarray:
+        """The number per reply (uint64; 0 where the reply is no publication) of the
+        last sequence() call."""
+        L = lib()
+        if not L.hvws_sequence_device(self.ctx):
+            _check(-2, "hvws_get_sequence")
+        n = L.hvws_reply_count(self.ctx)
+        if n < 0:
+            _check(-2, "hvws_reply_count")
+        seq = np.zeros(n, dtype=np.uint64)
+        _check(L.hvws_get_sequence(self.ctx, seq.ctypes.data, 0, n), "hvws_get_sequence")
+        return seq
+
+    def sequence_totals(self) -> Tuple[int, int]:
+        """(publications numbered, distinct topics published to) of the last
+        sequence() call."""
+        out = (ctypes.c_uint64 * 2)()
+        _check(lib().hvws_get_sequence_totals(self.ctx, out), "hvws_get_sequence_totals")
+        return tuple(int(x) for x in out)
+
+    def envelope_sequenced_bound(self) -> int:
+        """hvws_envelope_sequenced_bound: the env_cap envelope_sequenced() needs
+        behind the last route() call (0: there is none).  No wait."""
+        return int(lib().hvws_envelope_sequenced_bound(self.ctx))
+
+    def envelope_sequenced(self, env, env_cap: int, flags: int = 0) -> None:
+        """hvws_envelope_sequenced behind the last sequence() call: envelope() with
+        the line 'M<topic> #<seq>\n' (ENV_SENDER: 'M<topic> <sender> #<seq>\n').
+        env_cap >= envelope_sequenced_bound().  Fills envelope()'s tables:
+        envelope_table(), fanout_enveloped() and retain_enveloped() follow.  No
+        wait."""
+        dev = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        _check(lib().hvws_envelope_sequenced(self.ctx, dev(env), env_cap, flags), "hvws_envelope_sequenced")
 
     def budget(self, budget, budget_all: int = (1 << 64) - 1, fragment: int = 0, masked: bool = False) -> None:
         """hvws_budget over the last fanout() call: every destination's deliveries

@@ -345,6 +345,23 @@ struct pass_envelope {
     }
 };
 
+// hvws_sequence: the head scan's scratch, the sort's two pair arrays (keys,
+// then values) and its histograms, the number per reply, {publications
+// numbered, distinct topics published to}.  Nothing goes up: no slot.  The
+// counters are the caller's.  route / rep / msg / gen: the route call
+// (pass_route::seq), the reply call, the message call and the scans it ran
+// behind.  numbered: the route call whose turn the counters last moved on for
+// (0: none) -- a turn is numbered once.
+struct pass_sequence {
+    dbuf scan, ping, pong, hist, seq, meta;
+    bool have = false;
+    uint64_t route = 0, rep = 0, msg = 0, gen = 0;
+    uint64_t numbered = 0;
+    void release(rel ph) {
+        if (ph == REL_DEVICE) free_all({&scan, &ping, &pong, &hist, &seq, &meta});
+    }
+};
+
 // hvws_budget: the size scan's scratch (the wire bytes before each delivery,
 // the scans' scratch), per destination count2 / kept bytes / flags / first2 /
 // byte_off, the kept table and the reply of each kept delivery, {kept
@@ -516,6 +533,7 @@ struct hvws_ctx {
     pass_route rt;
     pass_retain rn;
     pass_envelope en;
+    pass_sequence sq;
     pass_budget bg;
     pass_subs subs;
     pass_check ck;
@@ -2594,6 +2612,7 @@ void hvws_ctx_destroy(hvws_ctx* c) {
         c->rt.release(ph);
         c->rn.release(ph);
         c->en.release(ph);
+        c->sq.release(ph);
         c->bg.release(ph);
         c->subs.release(ph);
         c->ck.release(ph);
@@ -4318,13 +4337,13 @@ int hvws_get_retain_totals(hvws_ctx* c, uint64_t out[5]) {
 
 uint64_t hvws_retain_tile(void) { return RETAIN_TILE; }
 
-static_assert(HVWS_ENV_HDR_MAX == 23 && ENV_TILE <= 0xFFFFFFFFull, "envelope constants");
+static_assert(HVWS_ENV_HDR_MAX == 23 && HVWS_SEQ_HDR_MAX == 45 && ENV_TILE <= 0xFFFFFFFFull, "envelope constants");
 
 namespace {
-// out_cap + (HVWS_ENV_HDR_MAX + 15) * reply capacity + 16 (include/hvws.h); 0 where 64 bits do not hold it
-uint64_t envelope_bound(const hvws_ctx* c) {
+// out_cap + (hdr_max + 15) * reply capacity + 16 (include/hvws.h); 0 where 64 bits do not hold it
+uint64_t envelope_bound(const hvws_ctx* c, uint32_t hdr_max = HVWS_ENV_HDR_MAX) {
     const uint64_t out_cap = c->mg.dout ? c->mg.out_cap : 0, cap = c->rp.cap;   // cap < 2^32 - 1: hvws_route saw it
-    const uint64_t per = (HVWS_ENV_HDR_MAX + 15u) * cap + 16u;
+    const uint64_t per = (hdr_max + 15u) * cap + 16u;
     return out_cap > ~0ull - per ? 0 : out_cap + per;
 }
 }  // namespace
@@ -4333,25 +4352,23 @@ uint64_t hvws_envelope_bound(hvws_ctx* c) { return route_valid(c) ? envelope_bou
 
 uint32_t hvws_envelope_tile(void) { return (uint32_t)ENV_TILE; }
 
-// Every reply's outgoing bytes into the caller's second buffer, publications
-// behind their envelope line, and the rows that point there
-// (hvws_envelope.hip): one scan, the finish, the copy.  No wait.
-int hvws_envelope(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags) {
-    int rc = check_ctx(c);
-    if (rc) return rc;
+namespace {
+// What hvws_envelope and hvws_envelope_sequenced share once the route (and the
+// numbering) is known to stand: seq (null: hvws_envelope) is the number per
+// reply, hdr_max the longest line of the form.
+int envelope_run(hvws_ctx* c, const char* who, uint8_t* d_env, uint64_t env_cap, uint32_t flags, const uint64_t* seq,
+                 uint32_t hdr_max) {
     pass_envelope& p = c->en;
-    p.have = false;   // the tables are being rewritten
-    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_envelope without a preceding hvws_route");
-    if (flags & ~(uint32_t)HVWS_ENV_SENDER) return set_err(HVWS_EINVAL, "hvws_envelope: unknown flag bits");
-    if (!d_env || ((uintptr_t)d_env & 15u)) return set_err(HVWS_EINVAL, "hvws_envelope: d_env must be 16-byte aligned, not null");
-    const uint64_t bound = envelope_bound(c);
+    if (flags & ~(uint32_t)HVWS_ENV_SENDER) return set_err(HVWS_EINVAL, "%s: unknown flag bits", who);
+    if (!d_env || ((uintptr_t)d_env & 15u)) return set_err(HVWS_EINVAL, "%s: d_env must be 16-byte aligned, not null", who);
+    const uint64_t bound = envelope_bound(c, hdr_max);
     if (bound == 0 || env_cap < bound)
-        return set_err(HVWS_EINVAL, "hvws_envelope: env_cap = %llu, hvws_envelope_bound %llu", (unsigned long long)env_cap,
+        return set_err(HVWS_EINVAL, "%s: env_cap = %llu, %s_bound %llu", who, (unsigned long long)env_cap, who,
                        (unsigned long long)bound);
     const uint8_t* dout = c->mg.dout;
     const uint64_t out_cap = dout ? c->mg.out_cap : 0;
     if (ranges_overlap(d_env, env_cap, dout, out_cap))
-        return set_err(HVWS_EINVAL, "hvws_envelope: d_env and the message output overlap");
+        return set_err(HVWS_EINVAL, "%s: d_env and the message output overlap", who);
     const uint64_t cap = c->rp.cap, np = cap + 1;
     HIP_OR(p.scan.ensure(env_scratch_bytes(cap)), HVWS_ENOMEM);
     HIP_OR(p.rows.ensure((cap + 1) * sizeof(dtxmsg)), HVWS_ENOMEM);
@@ -4361,7 +4378,7 @@ int hvws_envelope(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags)
     const env_tables t{c->rt.rows.as<dtxmsg>(), c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(),
                        c->rp.piece.as<uint64_t>(), c->rp.scan.as<uint64_t>() + cap, cap, c->mg.msgs.as<dmsg>(),
                        c->mg.meta.as<uint64_t>(), c->mg.cap, c->rt.nseg, c->rt.in.as<uint32_t>(), dout, out_cap, d_env,
-                       env_cap, (flags & HVWS_ENV_SENDER) != 0};
+                       env_cap, (flags & HVWS_ENV_SENDER) != 0, seq};
     uint64_t* plan = p.plan.as<uint64_t>();
     const env_work w{p.scan.p, p.rows.as<dtxmsg>(), p.rrows.as<dtxmsg>(), plan, plan + np, plan + 2 * np, plan + 3 * np,
                      p.meta.as<uint64_t>()};
@@ -4378,6 +4395,18 @@ int hvws_envelope(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags)
     p.msg = c->mg.seq;
     p.gen = c->scan_gen;
     return HVWS_OK;
+}
+}  // namespace
+
+// Every reply's outgoing bytes into the caller's second buffer, publications
+// behind their envelope line, and the rows that point there
+// (hvws_envelope.hip): one scan, the finish, the copy.  No wait.
+int hvws_envelope(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    c->en.have = false;   // the tables are being rewritten
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_envelope without a preceding hvws_route");
+    return envelope_run(c, "hvws_envelope", d_env, env_cap, flags, nullptr, HVWS_ENV_HDR_MAX);
 }
 
 namespace {
@@ -4440,6 +4469,94 @@ int hvws_retain_enveloped(hvws_ctx* c, uint8_t* d_store, uint64_t slot, hvws_ret
     if (!envelope_valid(c)) return set_err(HVWS_EINVAL, "hvws_retain_enveloped without a preceding hvws_envelope");
     if (flags) return set_err(HVWS_EINVAL, "hvws_retain_enveloped: unknown flag bits");
     return retain_run(c, "hvws_retain_enveloped", c->en.rrows.as<dtxmsg>(), c->en.env, c->en.env_cap, d_store, slot, d_ret);
+}
+
+// Every publication's number in its topic, and the caller's counters moved on
+// (hvws_seq.hip): the pairs, the sort, one scan, the numbers, the counters.  No
+// wait.
+int hvws_sequence(hvws_ctx* c, uint64_t* d_seq, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    pass_sequence& p = c->sq;
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_sequence without a preceding hvws_route");
+    // a second numbering of one turn would skip numbers; the first one's table stands
+    if (p.numbered == c->rt.seq) return set_err(HVWS_EINVAL, "hvws_sequence: this hvws_route's turn is numbered already");
+    p.have = false;   // the table is being rewritten
+    if (flags) return set_err(HVWS_EINVAL, "hvws_sequence: unknown flag bits");
+    const uint32_t ntopics = c->rt.ntopics;
+    const uint8_t* dout = c->mg.dout;
+    const uint64_t out_cap = dout ? c->mg.out_cap : 0;
+    if (ntopics) {
+        if (!d_seq || ((uintptr_t)d_seq & 7u)) return set_err(HVWS_EINVAL, "hvws_sequence: d_seq must be 8-byte aligned, not null");
+        if (ranges_overlap(d_seq, (uint64_t)ntopics * 8, dout, out_cap))
+            return set_err(HVWS_EINVAL, "hvws_sequence: the counters and the message output overlap");
+    }
+    const uint64_t cap = c->rp.cap;   // < 2^32 - 1: hvws_route saw it
+    HIP_OR(p.scan.ensure(seq_scratch_bytes(cap)), HVWS_ENOMEM);
+    HIP_OR(p.ping.ensure(cap * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.pong.ensure(cap * 8 + 16), HVWS_ENOMEM);
+    HIP_OR(p.hist.ensure(fan_hist_words(cap) * 8), HVWS_ENOMEM);
+    HIP_OR(p.seq.ensure((cap + 1) * 8), HVWS_ENOMEM);
+    HIP_OR(p.meta.ensure(64), HVWS_ENOMEM);
+    const seq_tables t{c->rt.topic.as<uint32_t>(), c->rt.kind.as<uint8_t>(), c->rp.scan.as<uint64_t>() + cap, cap, ntopics,
+                       d_seq};
+    uint32_t* key[2] = {p.ping.as<uint32_t>(), p.pong.as<uint32_t>()};
+    const seq_work w{{key[0], key[1]}, {key[0] + cap, key[1] + cap}, p.hist.as<uint64_t>(), p.scan.p, p.seq.as<uint64_t>(),
+                     p.meta.as<uint64_t>()};
+    // the timed device work (hvws_last_kernel_ms): the whole pass
+    HIP_OR(timed_begin(c), HVWS_EHIP);
+    HIP_OR(launch_sequence(t, w, c->stream), HVWS_EHIP);
+    HIP_OR(timed_end(c), HVWS_EHIP);
+    p.have = true;
+    p.numbered = c->rt.seq;
+    p.route = c->rt.seq;
+    p.rep = c->rp.seq;
+    p.msg = c->mg.seq;
+    p.gen = c->scan_gen;
+    return HVWS_OK;
+}
+
+namespace {
+// The last hvws_sequence's table stands: no route, reply call, message call or scan since.
+bool sequence_valid(const hvws_ctx* c) {
+    return route_valid(c) && c->sq.have && c->sq.route == c->rt.seq && c->sq.rep == c->rp.seq && c->sq.msg == c->mg.seq &&
+           c->sq.gen == c->scan_gen;
+}
+int sequence_ctx(hvws_ctx* c) {
+    if (int rc = check_ctx(c)) return rc;
+    return sequence_valid(c) ? HVWS_OK : set_err(HVWS_EINVAL, "no hvws_sequence call yet");
+}
+}  // namespace
+
+const uint64_t* hvws_sequence_device(hvws_ctx* c) { return sequence_valid(c) ? c->sq.seq.as<uint64_t>() : nullptr; }
+
+int hvws_get_sequence(hvws_ctx* c, uint64_t* seq, uint64_t first, uint64_t n) {
+    if (int rc = sequence_ctx(c)) return rc;
+    const int64_t have = hvws_reply_count(c);
+    if (have < 0) return HVWS_EINVAL;
+    if (first > (uint64_t)have || n > (uint64_t)have - first) return set_err(HVWS_EINVAL, "reply range out of bounds");
+    if (n == 0) return HVWS_OK;
+    return read_rows(c, {{seq, c->sq.seq.as<uint64_t>() + first, n * 8}});
+}
+
+int hvws_get_sequence_totals(hvws_ctx* c, uint64_t out[2]) {
+    if (int rc = sequence_ctx(c)) return rc;
+    if (!out) return set_err(HVWS_EINVAL, "hvws_get_sequence_totals: null out");
+    return read_rows(c, {{out, c->sq.meta.as<uint64_t>(), 16}});
+}
+
+uint64_t hvws_envelope_sequenced_bound(hvws_ctx* c) { return route_valid(c) ? envelope_bound(c, HVWS_SEQ_HDR_MAX) : 0; }
+
+// hvws_envelope whose publication lines end in the number the last
+// hvws_sequence gave (hvws_envelope.hip, the sequenced form).  Fills the
+// tables of hvws_envelope.  No wait.
+int hvws_envelope_sequenced(hvws_ctx* c, uint8_t* d_env, uint64_t env_cap, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    c->en.have = false;   // the tables are being rewritten
+    if (!route_valid(c)) return set_err(HVWS_EINVAL, "hvws_envelope_sequenced without a preceding hvws_route");
+    if (!sequence_valid(c)) return set_err(HVWS_EINVAL, "hvws_envelope_sequenced without a preceding hvws_sequence");
+    return envelope_run(c, "hvws_envelope_sequenced", d_env, env_cap, flags, c->sq.seq.as<uint64_t>(), HVWS_SEQ_HDR_MAX);
 }
 
 static_assert(BF_OVER == HVWS_BF_OVER, "budget flag bits");

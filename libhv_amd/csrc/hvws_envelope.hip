@@ -1,7 +1,10 @@
 // hvws_envelope.hip -- the kernels of hvws_envelope (include/hvws.h has the
 // contract): every reply's outgoing bytes written once into a second device
 // buffer, publications with the line `M<topic>[ <sender>]\n` in front, and the
-// row table that points into it.  The reference has no counterpart: its
+// row table that points into it.  hvws_envelope_sequenced is the same pass with
+// the line `M<topic>[ <sender>] #<seq>\n`: env_of, the plan's load and the
+// finish take the form as a template parameter, the copy is plan-driven and
+// serves both.  The reference has no counterpart: its
 // onmessage is user code.  Runs over what hvws_route left: the routed rows,
 // topic and kind per reply.
 //
@@ -13,7 +16,8 @@
 //                places a row or a byte.
 //   the finish   one thread per reply: the row R'[i] (and its twin for
 //                hvws_retain_enveloped, whose length is 0 where the body is
-//                empty), the envelope's bytes (at most 23, byte stores) and,
+//                empty), the envelope's bytes (at most 23, sequenced 45, byte
+//                stores) and,
 //                where a body is to be copied, the reply's entry of the dense
 //                copy plan.
 //   the copy     the payload path.  Work is cut by destination tile of
@@ -29,9 +33,10 @@
 //                the body's last partial one.
 //
 // Traffic per reply: 24 B row + 4 B topic + 1 B kind (+ 8 B piece word, one
-// piece and 4 B of dest_of with HVWS_ENV_SENDER) read by the plan and again by
+// piece and 4 B of dest_of with HVWS_ENV_SENDER, 8 B of seq when sequenced) read
+// by the plan and again by
 // the finish, 40 B of scan state written and read, two 24 B rows written; per
-// copied reply 32 B of plan; per publication at most 23 B of envelope.  Per
+// copied reply 32 B of plan; per publication at most 23 B (45 B) of envelope.  Per
 // body byte: one read (plus at most 31 B around the body) and one write.
 #include "hvws_dev.h"
 
@@ -70,13 +75,28 @@ __device__ __forceinline__ uint32_t env_sender(const env_tables& t, uint64_t i) 
     return s < t.nseg ? t.dest_of[s] : ~0u;
 }
 
+// decimal digits of v: 1 .. 20
+__device__ __forceinline__ uint32_t env_digits64(uint64_t v) {
+    uint32_t n = 1;
+    uint64_t p = 10;
+#pragma unroll
+    for (uint32_t k = 0; k < 19; ++k) {
+        n += v >= p ? 1u : 0u;
+        p *= 10u;   // 10^19 < 2^64: no wrap within the loop's uses
+    }
+    return n;
+}
+
 // What reply i puts into d_env: h envelope bytes, then body bytes from src.
 // Selects, no early return (the compiler note of hvws_route.hip).
 struct env_reply {
     uint64_t src, body;
     uint32_t h, flags, key, topic, sender;
     bool pub, verb;
+    uint64_t seq;   // SEQ alone
 };
+// SEQ: the sequenced line, whose number is t.seq[i]
+template <bool SEQ>
 __device__ __forceinline__ env_reply env_of(const env_tables& t, uint64_t i) {
     const dtxmsg r = t.rows[i];
     const uint32_t k = t.kind[i];
@@ -90,15 +110,22 @@ __device__ __forceinline__ env_reply env_of(const env_tables& t, uint64_t i) {
     o.topic = t.topic[i];
     o.sender = t.sender && o.pub ? env_sender(t, i) : 0u;
     o.h = o.pub ? 2u + env_digits(o.topic) + (t.sender ? 1u + env_digits(o.sender) : 0u) : 0u;
+    if constexpr (SEQ) {
+        o.seq = o.pub ? t.seq[i] : 0;
+        o.h += o.pub ? 2u + env_digits64(o.seq) : 0u;   // SP '#' digits
+    } else {
+        o.seq = 0;
+    }
     return o;
 }
 
+template <bool SEQ>
 struct env_load {
     env_tables in;
     __device__ __forceinline__ env6 operator()(uint64_t i) const {
         env6 v{};
         if (i < env_replies(in)) {
-            const env_reply o = env_of(in, i);
+            const env_reply o = env_of<SEQ>(in, i);
             const uint64_t bytes = o.h + o.body;
             v.tiles = o.body ? ((o.h & 15u) + o.body + ENV_TILE - 1) / ENV_TILE : 0;
             v.span = (bytes + 15u) & ~15ull;
@@ -120,7 +147,23 @@ __device__ __forceinline__ void env_put_digits(uint8_t* p, uint32_t v, uint32_t 
     }
 }
 
+// v in decimal at p[0 .. nd), nd <= 20: three words of at most 9 digits, so that
+// the digits come from 32-bit arithmetic
+__device__ __forceinline__ void env_put_digits64(uint8_t* p, uint64_t v, uint32_t nd) {
+    const uint64_t q = v / 1000000000ull;
+    uint32_t w0 = (uint32_t)(v - q * 1000000000ull);
+    uint32_t w2 = (uint32_t)(q / 1000000000ull);
+    uint32_t w1 = (uint32_t)(q - (uint64_t)w2 * 1000000000ull);
+#pragma unroll
+    for (uint32_t k = 0; k < 20; ++k) {
+        uint32_t& w = k < 9 ? w0 : k < 18 ? w1 : w2;
+        if (k < nd) p[nd - 1 - k] = (uint8_t)('0' + w % 10u);
+        w /= 10u;
+    }
+}
+
 // One thread per reply (at least one thread).
+template <bool SEQ>
 __global__ __launch_bounds__(256) void k_env_finish(env_tables in, env_work w, const env6* __restrict__ ex,
                                                     const env6* __restrict__ total) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -133,7 +176,7 @@ __global__ __launch_bounds__(256) void k_env_finish(env_tables in, env_work w, c
         w.pl_tile[tot.ent] = tot.tiles;   // behind the last entry's tiles
     }
     if (i >= env_replies(in)) return;
-    const env_reply o = env_of(in, i);
+    const env_reply o = env_of<SEQ>(in, i);
     const env6 b = ex[i];
     const uint64_t e = b.span, bytes = o.h + o.body;
     // the caller's env_cap covers every turn (hvws_envelope_bound); a reply that
@@ -153,9 +196,21 @@ __global__ __launch_bounds__(256) void k_env_finish(env_tables in, env_work w, c
         const uint32_t nt = env_digits(o.topic);
         p[0] = 'M';
         env_put_digits(p + 1, o.topic, nt);
-        if (in.sender) {
-            p[1 + nt] = ' ';
-            env_put_digits(p + 2 + nt, o.sender, o.h - nt - 3u);
+        if constexpr (SEQ) {
+            const uint32_t nq = env_digits64(o.seq);
+            const uint32_t at = o.h - nq - 3u;   // the SP before '#'
+            if (in.sender) {
+                p[1 + nt] = ' ';
+                env_put_digits(p + 2 + nt, o.sender, at - nt - 2u);
+            }
+            p[at] = ' ';
+            p[at + 1] = '#';
+            env_put_digits64(p + at + 2, o.seq, nq);
+        } else {
+            if (in.sender) {
+                p[1 + nt] = ' ';
+                env_put_digits(p + 2 + nt, o.sender, o.h - nt - 3u);
+            }
         }
         p[o.h - 1] = 0x0Au;
     }
@@ -238,10 +293,17 @@ hipError_t launch_envelope(const env_tables& t, const env_work& w, hipStream_t s
     env6* ex = reinterpret_cast<env6*>(w.scratch);
     env6* total = ex + t.rep_cap;   // one value; 16 are set aside
     env6* tmp = ex + t.rep_cap + 16;
-    hipError_t e = launch_scan_of(env_load{t}, ex, t.rep_cap, tmp, total, st);
-    if (e != hipSuccess) return e;
     const uint64_t fb = std::max<uint64_t>((t.rep_cap + 255) / 256, 1);
-    hipLaunchKernelGGL(k_env_finish, dim3((uint32_t)fb), dim3(256), 0, st, t, w, ex, total);
+    hipError_t e;
+    if (t.seq) {   // hvws_envelope_sequenced
+        e = launch_scan_of(env_load<true>{t}, ex, t.rep_cap, tmp, total, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_env_finish<true>, dim3((uint32_t)fb), dim3(256), 0, st, t, w, ex, total);
+    } else {
+        e = launch_scan_of(env_load<false>{t}, ex, t.rep_cap, tmp, total, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_env_finish<false>, dim3((uint32_t)fb), dim3(256), 0, st, t, w, ex, total);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (t.rep_cap == 0) return hipSuccess;
     // the tile count is on the device alone: a grid that covers the most tiles

@@ -910,6 +910,10 @@ struct env_tables {
     uint8_t* env;
     uint64_t env_cap;
     bool sender;   // HVWS_ENV_SENDER
+    // hvws_envelope_sequenced: the number per reply that launch_sequence left
+    // (rep_cap entries); a publication's line then ends ` #<seq>`.  Null:
+    // hvws_envelope.  The host picks the kernels by it; no kernel tests it.
+    const uint64_t* seq = nullptr;
 };
 // What they write besides: scratch (env_scratch_bytes(rep_cap)), the enveloped
 // rows (rep_cap entries; rrows: the same with length 0 where a publication's
@@ -932,6 +936,34 @@ uint64_t env_scratch_bytes(uint64_t cap);
 // 16) of a copied row, nor out[0, out_cap); no write leaves reply i's [e_i, e_i +
 // bytes), nor env[0, env_cap).
 hipError_t launch_envelope(const env_tables& t, const env_work& w, hipStream_t st);
+// hvws_sequence (hvws_seq.hip; include/hvws.h has the contract).  What its
+// kernels read: topic and kind per reply that launch_route left, the reply
+// count word clamped to rep_cap, and the caller's counter d_seq[t] of every
+// topic published to this turn.  They write d_seq[t] of those topics alone.
+struct seq_tables {
+    const uint32_t* topic;
+    const uint8_t* kind;
+    const uint64_t* nrep_dev;
+    uint64_t rep_cap;
+    uint32_t ntopics;
+    uint64_t* d_seq;
+};
+// What they write besides: the sort's pair arrays (rep_cap words each) and hist
+// (fan_hist_words(rep_cap)), scratch (seq_scratch_bytes(rep_cap)), seq (rep_cap
+// entries: the number of a publication, 0 for every other slot), meta (8
+// words): [0..1] = publications numbered, distinct topics published to.
+struct seq_work {
+    uint32_t* key[2];
+    uint32_t* val[2];
+    uint64_t* hist;
+    void* scratch;
+    uint64_t* seq;
+    uint64_t* meta;
+};
+uint64_t seq_scratch_bytes(uint64_t cap);
+// The whole pass, no wait.  No read or write leaves d_seq[0 .. ntopics); the
+// counters are stored by a kernel of their own behind the one that reads them.
+hipError_t launch_sequence(const seq_tables& t, const seq_work& w, hipStream_t st);
 // hvws_check (hvws_check.hip; include/hvws.h has the rule).  Reads the frame
 // table's info / length (nfr_dev, cap as for launch_utf8), bases, the piece
 // table of hvws_messages_rfc (mg_meta[2] pieces clamped to pcap), at most 125
